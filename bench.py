@@ -9,6 +9,12 @@ Weak scaling: every rank owns a 256^3 subdomain (z-slab of a global
 (tolerance 1e-6, RELATIVE_INI) from scratch. Rank 0 prints ONE JSON line.
 
     python bench.py --gpus N --steps K --warmup W [--size 256] [--config ...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line;
+--dump-outputs DIR additionally stores the last timed step's solution and
+residual history as .npy. --full is where secondary measurements belong;
+there are none today, so it changes nothing.
 """
 
 import argparse
@@ -188,7 +194,33 @@ def run_step(A, cfg, res, b):
         "iterations": st.iterations,
         "converged": bool(st.converged),
         "residual": st.residuals[-1] / st.residuals[0] if st.residuals else None,
-    }
+    }, x, st
+
+
+# --dump-outputs budget: 64 MB in all; the solution gets 32 MB, the residual
+# history is a few hundred bytes
+DUMP_MAX_X_ELEMS = (32 << 20) // 8
+
+
+def dump_outputs(out_dir, x_user, st, rank, world):
+    """Write what the last timed step handed back to its caller: the
+    solution x (user ordering, this rank's rows) and the residual-norm
+    history. A solution over the budget is stored as a fixed seeded sample
+    of its entries (ascending index order), so two builds run with the same
+    arguments dump comparable arrays."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    xs = x_user.detach().reshape(-1)
+    n = xs.numel()
+    if n > DUMP_MAX_X_ELEMS:
+        idx = np.sort(np.random.default_rng(20240).choice(
+            n, DUMP_MAX_X_ELEMS, replace=False))
+        xs = xs[torch.from_numpy(idx).to(xs.device)]
+    np.save(os.path.join(out_dir, f"x{suffix}.npy"),
+            xs.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(out_dir, f"residual_history{suffix}.npy"),
+            np.asarray([np.asarray(r, dtype=np.float64)
+                        for r in st.residuals], dtype=np.float64))
 
 
 def main():
@@ -204,7 +236,17 @@ def main():
     ap.add_argument("--device", default=None)
     ap.add_argument("--config", default="fgmres_agg", choices=sorted(CONFIGS),
                     help="solver composition (driver contract: fgmres_agg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "solution (x.npy; a fixed seeded sample when over "
+                         "32 MB) and residual_history.npy as float64 to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks; "
+                         "this benchmark has none beyond the timed steps, so "
+                         "the run is the same as a plain one")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -245,9 +287,16 @@ def main():
 
     barrier_sync()
     t_start = time.perf_counter()
-    stats = [run_step(A, cfg, res, b) for _ in range(args.steps)]
+    stats = []
+    for _ in range(args.steps):
+        s, x_last, st_last = run_step(A, cfg, res, b)
+        stats.append(s)
     barrier_sync()
     t_total = time.perf_counter() - t_start
+
+    if args.dump_outputs:
+        x_user = manager.permute_out(x_last) if manager is not None else x_last
+        dump_outputs(args.dump_outputs, x_user, st_last, rank, world)
 
     # max over ranks of the timed window
     if dist is not None:

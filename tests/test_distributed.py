@@ -496,12 +496,18 @@ def test_bench_contract_two_ranks():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # each rank takes the GPU of its local rank: with a single GPU the two
+    # ranks run on the host (gloo) path, as on a machine without one
+    env = dict(os.environ)
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env["HIP_VISIBLE_DEVICES"] = ""
+        env["CUDA_VISIBLE_DEVICES"] = ""
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29621", os.path.join(repo, "bench.py"),
          "--gpus", "2", "--steps", "1", "--warmup", "0", "--size", "10"],
-        capture_output=True, text=True, timeout=300, cwd=repo)
+        capture_output=True, text=True, timeout=300, cwd=repo, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -16,6 +16,18 @@ def run_py(script, *args, timeout=180):
         capture_output=True, text=True, timeout=timeout, cwd=REPO)
 
 
+def two_rank_env():
+    """Environment for a 2-rank launch: each rank takes the GPU of its local
+    rank, so with a single GPU the ranks run on the host (gloo) path, as
+    they do on a machine without one."""
+    import torch
+    env = dict(os.environ)
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env["HIP_VISIBLE_DEVICES"] = ""
+        env["CUDA_VISIBLE_DEVICES"] = ""
+    return env
+
+
 def test_example_capi_matrix_mtx():
     """BASELINE config #1: matrix.mtx + FGMRES_AGGREGATION on the host
     path must converge in 1 iteration (reference README.md:126-129 shows
@@ -73,5 +85,6 @@ def test_example_mpi_capi_two_ranks():
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29719", "examples/amgx_mpi_capi.py"],
-        capture_output=True, text=True, timeout=300, cwd=REPO)
+        capture_output=True, text=True, timeout=300, cwd=REPO,
+        env=two_rank_env())
     assert p.returncode == 0, (p.stdout[-400:], p.stderr[-800:])
