@@ -52,6 +52,18 @@ inline void check_dev(const Tensor& t) {
     TORCH_CHECK(t.is_cuda(), "amgx_amd._core requires device tensors");
 }
 
+// f(c, s, e) for every non-empty color c = slots [s, e) of rows_sorted, in
+// ascending or descending color order
+template <typename F>
+void for_each_color(const std::vector<int64_t>& bounds, bool ascending, F f) {
+    int nc = (int)bounds.size() - 1;
+    for (int k = 0; k < nc; ++k) {
+        int c = ascending ? k : nc - 1 - k;
+        int64_t s = bounds[c], e = bounds[c + 1];
+        if (e > s) f(c, s, e);
+    }
+}
+
 // ---------------------------------------------------------------- SpMV
 void csrmv(Tensor ro, Tensor ci, Tensor va, int64_t block_dim, Tensor x,
            Tensor y, c10::optional<Tensor> bvec, double alpha, double beta,
@@ -277,11 +289,8 @@ void gs_sweep(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
               Tensor bvec, Tensor x, Tensor rows_sorted,
               std::vector<int64_t> bounds, double omega, bool symmetric) {
     int n = (int)(ro.numel() - 1);
-    int nc = (int)bounds.size() - 1;
     DISPATCH_FT2(va, x, "gs_sweep", [&] {
-        auto run = [&](int c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) return;
+        auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_smooth_rows<scalar_a, scalar_v>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(),
                 va.data_ptr<scalar_a>(), dinv.data_ptr<scalar_a>(),
@@ -289,35 +298,31 @@ void gs_sweep(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 (scalar_v)omega, n, (int)b, cur_stream());
         };
-        for (int c = 0; c < nc; ++c) run(c);
-        if (symmetric)
-            for (int c = nc - 1; c >= 0; --c) run(c);
+        for_each_color(bounds, true, run);
+        if (symmetric) for_each_color(bounds, false, run);
     });
 }
 
 // color-sorted scalar GS sweep (reorder-by-color layout)
 void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
                      Tensor bvec, Tensor x, Tensor rows_sorted,
-                     std::vector<int64_t> bounds,
-                     c10::optional<Tensor> bounds_dev, double omega,
-                     bool symmetric) {
+                     std::vector<int64_t> bounds, Tensor bounds_dev,
+                     double omega, bool symmetric) {
     int nc = (int)bounds.size() - 1;
     int64_t n = (int64_t)ro_s.numel() - 1;
-    if (n <= 16384 && bounds_dev.has_value()) {
+    if (n <= amgx_hip::SMALL_LEVEL_ROWS) {
         DISPATCH_FT2(va_s, x, "gs_sweep_small", [&] {
             amgx_hip::gs_sweep_small<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>(), ci_s.data_ptr<int>(),
                 va_s.data_ptr<scalar_a>(), dinv_s.data_ptr<scalar_a>(),
                 bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                rows_sorted.data_ptr<int>(), bounds_dev->data_ptr<int>(),
+                rows_sorted.data_ptr<int>(), bounds_dev.data_ptr<int>(),
                 nc, (scalar_v)omega, symmetric, cur_stream());
         });
         return;
     }
     DISPATCH_FT2(va_s, x, "gs_sweep_sorted", [&] {
-        auto run = [&](int c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) return;
+        auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_rows_sorted<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
                 va_s.data_ptr<scalar_a>(), dinv_s.data_ptr<scalar_a>() + s,
@@ -325,9 +330,8 @@ void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 (scalar_v)omega, cur_stream());
         };
-        for (int c = 0; c < nc; ++c) run(c);
-        if (symmetric)
-            for (int c = nc - 1; c >= 0; --c) run(c);
+        for_each_color(bounds, true, run);
+        if (symmetric) for_each_color(bounds, false, run);
     });
 }
 
@@ -338,169 +342,70 @@ Tensor dilu_setup(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor didx,
     int n = (int)(ro.numel() - 1);
     auto einv = b == 1 ? torch::zeros({n}, va.options())
                        : torch::zeros({n, b, b}, va.options());
-    int nc = (int)bounds.size() - 1;
     DISPATCH_FT(va, "dilu_setup", [&] {
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, true, [&](int c, int64_t s, int64_t e) {
             amgx_hip::dilu_setup_color<scalar_t>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(),
                 va.data_ptr<scalar_t>(), didx.data_ptr<int>(),
                 tidx.data_ptr<int>(), colors.data_ptr<int>(),
                 rows_sorted.data_ptr<int>() + s, (int)(e - s), c,
                 einv.data_ptr<scalar_t>(), (int)b, cur_stream());
-        }
+        });
     });
     return einv;
 }
 
-// full M^-1 apply: r given; w,z scratch (pre-allocated); x += relax*z
-void dilu_apply(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor einv,
-                Tensor colors, Tensor rows_sorted, std::vector<int64_t> bounds,
-                Tensor r, Tensor w, Tensor z, Tensor x, double relax) {
-    int n = (int)(ro.numel() - 1);
-    int nc = (int)bounds.size() - 1;
-    w.zero_();
-    z.zero_();
-    DISPATCH_FT2(va, x, "dilu_apply", [&] {
-        hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            amgx_hip::dilu_fwd_color<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_a>(), einv.data_ptr<scalar_a>(),
-                colors.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), c, r.data_ptr<scalar_v>(),
-                w.data_ptr<scalar_v>(), (int)b, st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            amgx_hip::dilu_bwd_color<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_a>(), einv.data_ptr<scalar_a>(),
-                colors.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), c, w.data_ptr<scalar_v>(),
-                z.data_ptr<scalar_v>(), (int)b, st);
-        }
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
-    });
-}
-
-// color-sorted DILU apply: matrix arrays in rows_sorted order (one
-// contiguous slab per color — reference reorder-by-color layout)
-void dilu_apply_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
-                       Tensor einv_s, Tensor rows_sorted,
-                       std::vector<int64_t> bounds,
-                       c10::optional<Tensor> bounds_dev, Tensor r, Tensor w,
-                       Tensor z, Tensor x, double relax) {
+// color-sorted DILU apply x += relax * M^{-1} rhs: matrix arrays in
+// rows_sorted order (one contiguous slab per color — reference
+// reorder-by-color layout); w, z pre-allocated scratch.
+// fused: rhs is b and the residual b - A x is folded into the forward
+// sweep (one matrix read fewer per smoother iteration than residual
+// kernel + apply); scalar and block-4 only.
+void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
+                 Tensor einv_s, Tensor rows_sorted,
+                 std::vector<int64_t> bounds, Tensor bounds_dev, Tensor rhs,
+                 Tensor w, Tensor z, Tensor x, double relax, bool fused) {
+    TORCH_CHECK(!fused || b == 1 || b == 4,
+                "dilu_sorted: no fused-residual kernel for block_dim ", b);
     int nc = (int)bounds.size() - 1;
     int bb = (int)(b * b);
     int64_t n = (int64_t)ro_s.numel() - 1;
     // small levels: ONE fused single-WG launch for the whole apply
     // (zeroing + all colors both sweeps + relaxed axpy)
-    if (b == 1 && n <= 16384 && bounds_dev.has_value()) {
-        DISPATCH_FT2(va_s, x, "dilu_apply_small", [&] {
-            amgx_hip::dilu_apply_small<scalar_a, scalar_v>(
+    if (b == 1 && n <= amgx_hip::SMALL_LEVEL_ROWS) {
+        DISPATCH_FT2(va_s, x, "dilu_small", [&] {
+            amgx_hip::dilu_small<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>(), ci_s.data_ptr<int>(),
                 va_s.data_ptr<scalar_a>(), einv_s.data_ptr<scalar_a>(),
-                rows_sorted.data_ptr<int>(), bounds_dev->data_ptr<int>(),
-                nc, r.data_ptr<scalar_v>(), w.data_ptr<scalar_v>(),
+                rows_sorted.data_ptr<int>(), bounds_dev.data_ptr<int>(), nc,
+                rhs.data_ptr<scalar_v>(), w.data_ptr<scalar_v>(),
                 z.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                (scalar_v)relax, (long long)w.numel(), cur_stream());
+                (scalar_v)relax, (long long)w.numel(), fused, cur_stream());
         });
         return;
     }
     w.zero_();
     z.zero_();
-    DISPATCH_FT2(va_s, x, "dilu_apply_sorted", [&] {
+    DISPATCH_FT2(va_s, x, "dilu_sorted", [&] {
         hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        const scalar_v* xres = fused ? x.data_ptr<scalar_v>() : nullptr;
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_fwd_sorted<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
                 va_s.data_ptr<scalar_a>(),
                 einv_s.data_ptr<scalar_a>() + s * bb,
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                r.data_ptr<scalar_v>(), w.data_ptr<scalar_v>(), (int)b, st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            amgx_hip::dilu_bwd_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(),
-                einv_s.data_ptr<scalar_a>() + s * bb,
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                w.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), (int)b, st);
-        }
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
-    });
-}
-
-// fused-residual DILU smoother application: x += relax * M^{-1}(b - A x)
-// with the residual folded into the forward sweep (one matrix read fewer
-// per smoother iteration than residual-kernel + apply)
-void dilu_smooth_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
-                        Tensor einv_s, Tensor rows_sorted,
-                        std::vector<int64_t> bounds,
-                        c10::optional<Tensor> bounds_dev, Tensor bvec,
-                        Tensor x, Tensor w, Tensor z, double relax) {
-    int nc = (int)bounds.size() - 1;
-    int bb = (int)(b * b);
-    int64_t n = (int64_t)ro_s.numel() - 1;
-    if (b == 1 && n <= 16384 && bounds_dev.has_value()) {
-        DISPATCH_FT2(va_s, x, "dilu_smooth_small", [&] {
-            amgx_hip::dilu_smooth_small<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>(), ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(), einv_s.data_ptr<scalar_a>(),
-                rows_sorted.data_ptr<int>(), bounds_dev->data_ptr<int>(),
-                nc, bvec.data_ptr<scalar_v>(), w.data_ptr<scalar_v>(),
-                z.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                (scalar_v)relax, (long long)w.numel(), cur_stream());
+                rhs.data_ptr<scalar_v>(), xres, w.data_ptr<scalar_v>(),
+                (int)b, st);
         });
-        return;
-    }
-    w.zero_();
-    z.zero_();
-    DISPATCH_FT2(va_s, x, "dilu_smooth_sorted", [&] {
-        hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            if (b == 4)
-                amgx_hip::dilu_fwd_b4_sorted_fused<scalar_a, scalar_v>(
-                    ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                    va_s.data_ptr<scalar_a>(),
-                    einv_s.data_ptr<scalar_a>() + s * bb,
-                    rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                    bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                    w.data_ptr<scalar_v>(), st);
-            else
-                amgx_hip::dilu_fwd_sorted_fused<scalar_a, scalar_v>(
-                    ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                    va_s.data_ptr<scalar_a>(),
-                    einv_s.data_ptr<scalar_a>() + s * bb,
-                    rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                    bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                    w.data_ptr<scalar_v>(), st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_bwd_sorted<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
                 va_s.data_ptr<scalar_a>(),
                 einv_s.data_ptr<scalar_a>() + s * bb,
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 w.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), (int)b, st);
-        }
+        });
         amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
                                  z.data_ptr<scalar_v>(), (scalar_v)relax,
                                  x.numel(), st);
@@ -618,22 +523,6 @@ void gather(Tensor src, Tensor idx, int64_t b, Tensor dst) {
                                    idx.data_ptr<int>(), (int)idx.numel(),
                                    (int)b, dst.data_ptr<scalar_t>(),
                                    cur_stream());
-    });
-}
-
-void scatter(Tensor src, Tensor idx, int64_t b, Tensor dst, bool add) {
-    DISPATCH_FT(src, "scatter", [&] {
-        if (add)
-            amgx_hip::scatter_add<scalar_t>(src.data_ptr<scalar_t>(),
-                                            idx.data_ptr<int>(),
-                                            (int)idx.numel(), (int)b,
-                                            dst.data_ptr<scalar_t>(),
-                                            cur_stream());
-        else
-            amgx_hip::scatter<scalar_t>(src.data_ptr<scalar_t>(),
-                                        idx.data_ptr<int>(), (int)idx.numel(),
-                                        (int)b, dst.data_ptr<scalar_t>(),
-                                        cur_stream());
     });
 }
 
@@ -802,16 +691,13 @@ Tensor ilu0_setup(Tensor ro, Tensor ci, Tensor va, Tensor didx, Tensor pos,
                   Tensor rows_sorted, std::vector<int64_t> bounds) {
     int n = (int)(ro.numel() - 1);
     auto lu = va.clone();
-    int nc = (int)bounds.size() - 1;
     DISPATCH_FT(va, "ilu0_setup", [&] {
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_factor_color_launch<scalar_t>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
                 didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
                 (int)(e - s), lu.data_ptr<scalar_t>(), n, cur_stream());
-        }
+        });
     });
     return lu;
 }
@@ -824,12 +710,9 @@ std::vector<Tensor> ilu0_setup_block(Tensor ro, Tensor ci, Tensor va,
     int n = (int)(ro.numel() - 1);
     auto lu = va.clone().reshape({-1});
     auto dinv = torch::zeros({(int64_t)n * b * b}, va.options());
-    int nc = (int)bounds.size() - 1;
     DISPATCH_FT(va, "ilu0_setup_block", [&] {
         hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_factor_color_block_launch<scalar_t>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
                 didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
@@ -839,7 +722,7 @@ std::vector<Tensor> ilu0_setup_block(Tensor ro, Tensor ci, Tensor va,
                 didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
                 (int)(e - s), lu.data_ptr<scalar_t>(),
                 dinv.data_ptr<scalar_t>(), (int)b, st);
-        }
+        });
     });
     return {lu, dinv};
 }
@@ -849,99 +732,56 @@ void ilu0_apply_block(Tensor ro, Tensor ci, Tensor lu, Tensor dinv,
                       std::vector<int64_t> bounds, Tensor r, Tensor y,
                       Tensor z, Tensor x, double relax) {
     int n = (int)(ro.numel() - 1);
-    int nc = (int)bounds.size() - 1;
     y.zero_();
     z.zero_();
     DISPATCH_FT2(lu, x, "ilu0_apply_block", [&] {
         hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_fwd_block_launch<scalar_a, scalar_v>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
                 lu.data_ptr<scalar_a>(), rows_sorted.data_ptr<int>() + s,
                 (int)(e - s), r.data_ptr<scalar_v>(),
                 y.data_ptr<scalar_v>(), n, (int)b, st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        });
+        for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_bwd_block_launch<scalar_a, scalar_v>(
                 ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
                 lu.data_ptr<scalar_a>(), dinv.data_ptr<scalar_a>(),
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 y.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), n, (int)b,
                 st);
-        }
+        });
         amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
                                  z.data_ptr<scalar_v>(), (scalar_v)relax,
                                  x.numel(), st);
     });
 }
 
-// color-sorted ILU(0) apply (reorder-by-color slabs; cf. dilu_apply_sorted)
+// color-sorted ILU(0) apply (reorder-by-color slabs; cf. dilu_sorted)
 void ilu0_apply_sorted(Tensor ro_s, Tensor ci_s, Tensor lu_s, Tensor diag_s,
                        Tensor pos, Tensor rows_sorted,
                        std::vector<int64_t> bounds, Tensor r, Tensor y,
                        Tensor z, Tensor x, double relax) {
     int n = (int)(ro_s.numel() - 1);
-    int nc = (int)bounds.size() - 1;
     y.zero_();
     z.zero_();
     DISPATCH_FT2(lu_s, x, "ilu0_apply_sorted", [&] {
         hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_fwd_sorted<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
                 lu_s.data_ptr<scalar_a>(), pos.data_ptr<int>(),
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 r.data_ptr<scalar_v>(), y.data_ptr<scalar_v>(), n, st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
+        });
+        for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_bwd_sorted<scalar_a, scalar_v>(
                 ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
                 lu_s.data_ptr<scalar_a>(),
                 diag_s.data_ptr<scalar_a>() + s, pos.data_ptr<int>(),
                 rows_sorted.data_ptr<int>() + s, (int)(e - s),
                 y.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), n, st);
-        }
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
-    });
-}
-
-void ilu0_apply(Tensor ro, Tensor ci, Tensor lu, Tensor didx, Tensor pos,
-                Tensor rows_sorted, std::vector<int64_t> bounds, Tensor r,
-                Tensor y, Tensor z, Tensor x, double relax) {
-    int n = (int)(ro.numel() - 1);
-    int nc = (int)bounds.size() - 1;
-    y.zero_();
-    z.zero_();
-    DISPATCH_FT2(lu, x, "ilu0_apply", [&] {
-        hipStream_t st = cur_stream();
-        for (int c = 0; c < nc; ++c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            amgx_hip::ilu0_fwd_launch<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                lu.data_ptr<scalar_a>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), r.data_ptr<scalar_v>(), y.data_ptr<scalar_v>(),
-                n, st);
-        }
-        for (int c = nc - 1; c >= 0; --c) {
-            int64_t s = bounds[c], e = bounds[c + 1];
-            if (e <= s) continue;
-            amgx_hip::ilu0_bwd_launch<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                lu.data_ptr<scalar_a>(), didx.data_ptr<int>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                y.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), n, st);
-        }
+        });
         amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
                                  z.data_ptr<scalar_v>(), (scalar_v)relax,
                                  x.numel(), st);
@@ -951,6 +791,7 @@ void ilu0_apply(Tensor ro, Tensor ci, Tensor lu, Tensor didx, Tensor pos,
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.attr("SMALL_LEVEL_ROWS") = amgx_hip::SMALL_LEVEL_ROWS;
     m.def("csrmv", &csrmv);
     m.def("reduce_op", &reduce_op);
     m.def("axpy", &axpy);
@@ -970,9 +811,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gs_sweep", &gs_sweep);
     m.def("gs_sweep_sorted", &gs_sweep_sorted);
     m.def("dilu_setup", &dilu_setup);
-    m.def("dilu_apply", &dilu_apply);
-    m.def("dilu_apply_sorted", &dilu_apply_sorted);
-    m.def("dilu_smooth_sorted", &dilu_smooth_sorted);
+    m.def("dilu_sorted", &dilu_sorted);
     m.def("color_minmax", &color_minmax);
     m.def("size2_match", &size2_match);
     m.def("restrict_agg", &restrict_agg);
@@ -980,7 +819,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("prolongate_agg", &prolongate_agg);
     m.def("dense_gemv", &dense_gemv);
     m.def("gather", &gather);
-    m.def("scatter", &scatter);
     m.def("galerkin_agg", &galerkin_agg);
     m.def("spgemm", &spgemm);
     m.def("transpose", &transpose);
@@ -993,5 +831,4 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ilu0_setup_block", &ilu0_setup_block);
     m.def("ilu0_apply_sorted", &ilu0_apply_sorted);
     m.def("ilu0_apply_block", &ilu0_apply_block);
-    m.def("ilu0_apply", &ilu0_apply);
 }

@@ -45,7 +45,13 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
                       int** big_rows_out, int* n_big_out, hipStream_t s);
 void free_device_buf(void* p, hipStream_t s);
 
-// ---- color-sorted GS sweep (reorder-by-color layout) ------------------------
+// ---- color-sorted sweeps (reorder-by-color layout) -------------------------
+// Matrix arrays are the rows_sorted-gathered copy, so each color reads one
+// contiguous slab. Levels of at most SMALL_LEVEL_ROWS rows run the whole
+// sweep in one single-workgroup launch (*_small); larger levels launch once
+// per color with ro_s/rows/dinv_s/einv_s pre-offset to the color base.
+constexpr int SMALL_LEVEL_ROWS = 1 << 14;
+
 template <typename TA, typename TV>
 void gs_sweep_small(const int* ro_s, const int* ci_s, const TA* va_s,
                     const TA* dinv_s, const TV* bvec, TV* x, const int* rows,
@@ -56,35 +62,21 @@ void gs_rows_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                     const TA* dinv_s, const TV* bvec, TV* x, const int* rows,
                     int count, TV omega, hipStream_t s);
 
-// ---- color-sorted DILU sweeps (reorder-by-color layout) ---------------------
-// ro_s/rows/einv_s pre-offset to the color base; matrix arrays are the
-// rows_sorted-gathered copy so each color reads one contiguous slab.
-// fused whole-apply for small levels: one single-WG launch does zeroing,
-// all forward colors, all backward colors and the relaxed axpy
+// DILU: x += relax * M^{-1} rhs.  Fused-residual form: rhs = b and the
+// forward gather adds x (xres), so M^{-1}(b - A x) costs one matrix read
+// less; scalar and block-4 only.
+// whole apply for small scalar levels: zeroing, all forward colors, all
+// backward colors and the relaxed axpy
 template <typename TA, typename TV>
-void dilu_apply_small(const int* ro_s, const int* ci_s, const TA* va_s,
-                      const TA* einv_s, const int* rows, const int* bounds,
-                      int ncolors, const TV* r, TV* w, TV* z, TV* x,
-                      TV relax, long long vec_n, hipStream_t s);
-template <typename TA, typename TV>
-void dilu_fwd_sorted_fused(const int* ro_s, const int* ci_s, const TA* va_s,
-                           const TA* einv_s, const int* rows, int count,
-                           const TV* bvec, const TV* x, TV* w,
-                           hipStream_t s);
-template <typename TA, typename TV>
-void dilu_smooth_small(const int* ro_s, const int* ci_s, const TA* va_s,
-                       const TA* einv_s, const int* rows, const int* bounds,
-                       int ncolors, const TV* bvec, TV* w, TV* z, TV* x,
-                       TV relax, long long vec_n, hipStream_t s);
-template <typename TA, typename TV>
-void dilu_fwd_b4_sorted_fused(const int* ro_s, const int* ci_s,
-                              const TA* va_s, const TA* einv_s,
-                              const int* rows, int count, const TV* bvec,
-                              const TV* x, TV* w, hipStream_t s);
+void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
+                const TA* einv_s, const int* rows, const int* bounds,
+                int ncolors, const TV* rhs, TV* w, TV* z, TV* x, TV relax,
+                long long vec_n, bool fused, hipStream_t s);
 template <typename TA, typename TV>
 void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
-                     const TV* r, TV* w, int b, hipStream_t s);
+                     const TV* rhs, const TV* xres /* nullptr = plain */,
+                     TV* w, int b, hipStream_t s);
 template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
@@ -103,17 +95,10 @@ void bsrmv_bn(const int* ro, const int* ci, const TA* va, int b, const TV* x,
               TV* y, const TV* bvec, double alpha, double beta, double gamma,
               int row_begin, int row_end, hipStream_t s);
 template <typename TA, typename TV>
-void dilu_fwd_b4(const int* ro, const int* ci, const TA* va, const TA* einv,
-                 const int* rows, int count, const TV* r, TV* w,
-                 hipStream_t s);
-template <typename TA, typename TV>
-void dilu_bwd_b4(const int* ro, const int* ci, const TA* va, const TA* einv,
-                 const int* rows, int count, const TV* w, TV* z,
-                 hipStream_t s);
-template <typename TA, typename TV>
 void dilu_fwd_b4_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                         const TA* einv_s, const int* rows, int count,
-                        const TV* r, TV* w, hipStream_t s);
+                        const TV* r, const TV* xres /* nullptr = plain */,
+                        TV* w, hipStream_t s);
 template <typename TA, typename TV>
 void dilu_bwd_b4_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                         const TA* einv_s, const int* rows, int count,
@@ -173,17 +158,6 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
                       const int* didx, const int* tidx, const int* colors,
                       const int* rows, int count, int color, T* einv, int b,
                       hipStream_t s);
-template <typename TA, typename TV>
-void dilu_fwd_color(const int* ro, const int* ci, const TA* va,
-                    const TA* einv, const int* colors, const int* rows,
-                    int count, int color, const TV* r, TV* w, int b,
-                    hipStream_t s);
-template <typename TA, typename TV>
-void dilu_bwd_color(const int* ro, const int* ci, const TA* va,
-                    const TA* einv, const int* colors, const int* rows,
-                    int count, int color, const TV* w, TV* z, int b,
-                    hipStream_t s);
-
 // ---- coloring (setup.hip) ---------------------------------------------------
 // one min-max hash round; returns (via counter) number newly colored.
 void color_minmax_round(const int* ro, const int* ci, int n,
@@ -217,17 +191,10 @@ void prolongate_agg(T* x, const T* xc, const int* agg, int n, int b,
 template <typename TA, typename TV>
 void dense_gemv(const TA* Ainv, const TV* b, TV* x, int n, hipStream_t s);
 
-// ---- gather/scatter for halo pack (misc.hip) ---------------------------------
+// ---- gather for halo pack (misc.hip) -----------------------------------------
 template <typename T>
 void gather(const T* src, const int* idx, int count, int b, T* dst,
             hipStream_t s);
-template <typename T>
-void scatter(const T* src, const int* idx, int count, int b, T* dst,
-             hipStream_t s);
-template <typename T>
-void scatter_add(const T* src, const int* idx, int count, int b, T* dst,
-                 hipStream_t s);
-
 // ---- SpGEMM / Galerkin (kernels_setup.hip) ----------------------------------
 // Aggregation Galerkin: COO keys agg[i]*nc+agg[j] -> radix sort ->
 // reduce_by_key -> CSR. Returns nnz_c; fills ro_c (nc+1); ci_c/va_c are
@@ -287,14 +254,6 @@ template <typename T>
 void ilu0_factor_color_launch(const int* ro, const int* ci, const int* pos,
                               const int* didx, const int* rows, int count,
                               T* lu, int n, hipStream_t s);
-template <typename TA, typename TV>
-void ilu0_fwd_launch(const int* ro, const int* ci, const int* pos,
-                     const TA* lu, const int* rows, int count, const TV* r,
-                     TV* y, int n, hipStream_t s);
-template <typename TA, typename TV>
-void ilu0_bwd_launch(const int* ro, const int* ci, const int* pos,
-                     const TA* lu, const int* didx, const int* rows, int count,
-                     const TV* y, TV* z, int n, hipStream_t s);
 // color-sorted ILU(0) sweeps (reorder-by-color slabs)
 template <typename TA, typename TV>
 void ilu0_fwd_sorted(const int* ro_s, const int* ci_s, const TA* lu_s,

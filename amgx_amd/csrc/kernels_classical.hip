@@ -318,48 +318,6 @@ __global__ __launch_bounds__(AMGX_BLOCK) void ilu0_factor_color(const int* __res
     }
 }
 
-// forward: y_i = r_i - sum_{pos[j]<pos[i]} l_ij y_j (unit L); per color.
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void ilu0_fwd(const int* __restrict__ ro, const int* __restrict__ ci,
-                         const int* __restrict__ pos,
-                         const TA* __restrict__ lu,
-                         const int* __restrict__ rows, int count,
-                         const TV* __restrict__ r, TV* __restrict__ y, int n) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    int pi = pos[i];
-    TV sum = r[i];
-    for (int k = ro[i]; k < ro[i + 1]; ++k) {
-        int j = ci[k];
-        if (j < n && pos[j] < pi) sum -= (TV)lu[k] * y[j];
-    }
-    y[i] = sum;
-}
-
-// backward: z_i = (y_i - sum_{pos[j]>pos[i]} u_ij z_j) / u_ii; per color desc.
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void ilu0_bwd(const int* __restrict__ ro, const int* __restrict__ ci,
-                         const int* __restrict__ pos,
-                         const TA* __restrict__ lu,
-                         const int* __restrict__ didx,
-                         const int* __restrict__ rows, int count,
-                         const TV* __restrict__ y, TV* __restrict__ z, int n) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    int pi = pos[i];
-    TV sum = y[i];
-    for (int k = ro[i]; k < ro[i + 1]; ++k) {
-        int j = ci[k];
-        if (j < n && pos[j] > pi) sum -= (TV)lu[k] * z[j];
-    }
-    int dk = didx[i];
-    TV d = dk >= 0 ? (TV)lu[dk] : TV(1);
-    if (d == TV(0)) d = TV(1);
-    z[i] = sum / d;
-}
-
 // ------------------------------------------------------------ block ILU(0)
 // Same color-ordered elimination with b x b blocks (reference
 // src/solvers/multicolor_ilu_solver.cu block path):
@@ -579,6 +537,8 @@ void ilu0_bwd_block_launch(const int* ro, const int* ci, const int* pos,
 // ---------------------------------------------------- color-sorted sweeps
 // Same reorder-by-color slab layout as the DILU sweeps (kernels_solve.hip):
 // lu_s/ci_s are rows_sorted-gathered copies, diag_s the per-slot pivot.
+// forward: y_i = r_i - sum_{pos[j]<pos[i]} l_ij y_j (unit L); per color.
+// backward: z_i = (y_i - sum_{pos[j]>pos[i]} u_ij z_j) / u_ii; per color desc.
 template <typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void ilu0_fwd_sorted_kernel(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
@@ -646,24 +606,6 @@ void ilu0_factor_color_launch(const int* ro, const int* ci, const int* pos,
                        dim3(AMGX_BLOCK), 0, s, ro, ci, pos, didx, rows, count,
                        lu, n);
 }
-template <typename TA, typename TV>
-void ilu0_fwd_launch(const int* ro, const int* ci, const int* pos,
-                     const TA* lu, const int* rows, int count, const TV* r,
-                     TV* y, int n, hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((ilu0_fwd<TA, TV>), dim3(grid_1d(count)),
-                       dim3(AMGX_BLOCK), 0, s, ro, ci, pos, lu, rows, count,
-                       r, y, n);
-}
-template <typename TA, typename TV>
-void ilu0_bwd_launch(const int* ro, const int* ci, const int* pos,
-                     const TA* lu, const int* didx, const int* rows, int count,
-                     const TV* y, TV* z, int n, hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((ilu0_bwd<TA, TV>), dim3(grid_1d(count)),
-                       dim3(AMGX_BLOCK), 0, s, ro, ci, pos, lu, didx, rows,
-                       count, y, z, n);
-}
 
 #define INSTANTIATE_CLASSICAL(T)                                               \
     template void strength_ahat<T>(const int*, const int*, const T*,           \
@@ -682,12 +624,6 @@ void ilu0_bwd_launch(const int* ro, const int* ci, const int* pos,
     template void ilu0_bwd_sorted<T, T>(const int*, const int*, const T*,       \
                                         const T*, const int*, const int*,        \
                                         int, const T*, T*, int, hipStream_t);   \
-    template void ilu0_fwd_launch<T, T>(const int*, const int*, const int*,    \
-                                        const T*, const int*, int, const T*,   \
-                                        T*, int, hipStream_t);                 \
-    template void ilu0_bwd_launch<T, T>(const int*, const int*, const int*,    \
-                                        const T*, const int*, const int*,      \
-                                        int, const T*, T*, int, hipStream_t);  \
     template void ilu0_factor_color_block_launch<T>(                           \
         const int*, const int*, const int*, const int*, const int*, int, T*,  \
         const T*, int, int, hipStream_t);                                      \
@@ -703,15 +639,6 @@ void ilu0_bwd_launch(const int* ro, const int* ci, const int* pos,
 INSTANTIATE_CLASSICAL(double)
 INSTANTIATE_CLASSICAL(float)
 // mixed dDFI ILU apply: float factor, double vectors
-template void ilu0_fwd_launch<float, double>(const int*, const int*,
-                                             const int*, const float*,
-                                             const int*, int, const double*,
-                                             double*, int, hipStream_t);
-template void ilu0_bwd_launch<float, double>(const int*, const int*,
-                                             const int*, const float*,
-                                             const int*, const int*, int,
-                                             const double*, double*, int,
-                                             hipStream_t);
 template void ilu0_fwd_sorted<float, double>(const int*, const int*,
                                              const float*, const int*,
                                              const int*, int, const double*,

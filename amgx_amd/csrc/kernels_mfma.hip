@@ -59,17 +59,17 @@ void mfma4_probe(const double* a, const double* b, double* c, hipStream_t s) {
 // ---------------------------------------------------------------- DILU b=4
 // Forward sweep, one color: w_i = Einv_i (r_i - sum_{color(j)<c} A_ij w_j).
 // w is pre-zeroed outside so the full-row sum only picks up earlier colors.
-// SORTED=1 reads the color-sorted matrix copy (ro_s/einv_s indexed by slot,
-// pointers pre-offset to the color base).
-// FUSED=1 folds the residual into the sweep: the gather becomes
+// Reads the color-sorted matrix copy (ro_s/einv_s indexed by slot, pointers
+// pre-offset to the color base; see kernels_solve.hip).
+// FUSED folds the residual into the sweep: the gather becomes
 // x[j]+w[j] against the FULL row (incl. diagonal; w_i is still zero), so
 // w_i = Einv_i (b_i - A_i.x - sum_{earlier} A_ij w_j) in one matrix read.
-template <typename TA, typename TV, int SORTED, int FUSED = 0>
+template <typename TA, typename TV, bool FUSED>
 __global__ __launch_bounds__(256) void dilu_fwd_b4_kernel(
     const int* __restrict__ ro, const int* __restrict__ ci,
     const TA* __restrict__ va, const TA* __restrict__ einv,
     const int* __restrict__ rows, int count, const TV* __restrict__ r,
-    TV* __restrict__ w, const TV* __restrict__ xv = nullptr) {
+    TV* __restrict__ w, const TV* __restrict__ xv) {
     int lane = threadIdx.x & 63;
     int b = (lane >> 2) & 3;             // MFMA block = row within wave
     int o = lane >> 4;                   // k index of A/B frags
@@ -78,12 +78,9 @@ __global__ __launch_bounds__(256) void dilu_fwd_b4_kernel(
     bool valid = slot < count;
     int i = valid ? rows[slot] : 0;
     double acc = 0.0;
-    long long ebase;
+    long long ebase = (long long)slot * 16;
     if (valid) {
-        int k0, k1;
-        if (SORTED) { k0 = ro[slot]; k1 = ro[slot + 1];
-                      ebase = (long long)slot * 16; }
-        else { k0 = ro[i]; k1 = ro[i + 1]; ebase = (long long)i * 16; }
+        int k0 = ro[slot], k1 = ro[slot + 1];
         for (int k = k0; k < k1; ++k) {
             int j = ci[k];
             if (!FUSED && j == i) continue;
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256) void dilu_fwd_b4_kernel(
 }
 
 // Backward sweep, one color: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j.
-template <typename TA, typename TV, int SORTED>
+template <typename TA, typename TV>
 __global__ __launch_bounds__(256) void dilu_bwd_b4_kernel(
     const int* __restrict__ ro, const int* __restrict__ ci,
     const TA* __restrict__ va, const TA* __restrict__ einv,
@@ -118,12 +115,9 @@ __global__ __launch_bounds__(256) void dilu_bwd_b4_kernel(
     bool valid = slot < count;
     int i = valid ? rows[slot] : 0;
     double acc = 0.0;
-    long long ebase;
+    long long ebase = (long long)slot * 16;
     if (valid) {
-        int k0, k1;
-        if (SORTED) { k0 = ro[slot]; k1 = ro[slot + 1];
-                      ebase = (long long)slot * 16; }
-        else { k0 = ro[i]; k1 = ro[i + 1]; ebase = (long long)i * 16; }
+        int k0 = ro[slot], k1 = ro[slot + 1];
         for (int k = k0; k < k1; ++k) {
             int j = ci[k];
             if (j == i) continue;
@@ -221,46 +215,16 @@ __global__ __launch_bounds__(256) void dilu_setup_b4_kernel(
         einv[(long long)i * 16 + lane] = (TA)Is[wave][lane];
 }
 
-template <typename TA, typename TV>
-void dilu_fwd_b4(const int* ro, const int* ci, const TA* va, const TA* einv,
-                 const int* rows, int count, const TV* r, TV* w,
-                 hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_fwd_b4_kernel<TA, TV, 0>),
-                       dim3((count + 15) / 16), dim3(256), 0, s, ro, ci, va,
-                       einv, rows, count, r, w);
-}
-
-template <typename TA, typename TV>
-void dilu_bwd_b4(const int* ro, const int* ci, const TA* va, const TA* einv,
-                 const int* rows, int count, const TV* w, TV* z,
-                 hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_bwd_b4_kernel<TA, TV, 0>),
-                       dim3((count + 15) / 16), dim3(256), 0, s, ro, ci, va,
-                       einv, rows, count, w, z);
-}
-
-// color-sorted variants (reorder-by-color slabs; see kernels_solve.hip)
+// xres != nullptr selects the fused-residual sweep (r = b, xres = x)
 template <typename TA, typename TV>
 void dilu_fwd_b4_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                         const TA* einv_s, const int* rows, int count,
-                        const TV* r, TV* w, hipStream_t s) {
+                        const TV* r, const TV* xres, TV* w, hipStream_t s) {
     if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_fwd_b4_kernel<TA, TV, 1>),
-                       dim3((count + 15) / 16), dim3(256), 0, s, ro_s, ci_s,
-                       va_s, einv_s, rows, count, r, w);
-}
-
-template <typename TA, typename TV>
-void dilu_fwd_b4_sorted_fused(const int* ro_s, const int* ci_s,
-                              const TA* va_s, const TA* einv_s,
-                              const int* rows, int count, const TV* bvec,
-                              const TV* x, TV* w, hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_fwd_b4_kernel<TA, TV, 1, 1>),
-                       dim3((count + 15) / 16), dim3(256), 0, s, ro_s, ci_s,
-                       va_s, einv_s, rows, count, bvec, w, x);
+    auto kern = xres ? dilu_fwd_b4_kernel<TA, TV, true>
+                     : dilu_fwd_b4_kernel<TA, TV, false>;
+    hipLaunchKernelGGL(kern, dim3((count + 15) / 16), dim3(256), 0, s, ro_s,
+                       ci_s, va_s, einv_s, rows, count, r, w, xres);
 }
 
 template <typename TA, typename TV>
@@ -268,7 +232,7 @@ void dilu_bwd_b4_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                         const TA* einv_s, const int* rows, int count,
                         const TV* w, TV* z, hipStream_t s) {
     if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_bwd_b4_kernel<TA, TV, 1>),
+    hipLaunchKernelGGL((dilu_bwd_b4_kernel<TA, TV>),
                        dim3((count + 15) / 16), dim3(256), 0, s, ro_s, ci_s,
                        va_s, einv_s, rows, count, w, z);
 }
@@ -397,23 +361,12 @@ void bsrmv_bn(const int* ro, const int* ci, const TA* va, int b,
 
 // ------------------------------------------------------------ instantiation
 #define INSTANTIATE_MFMA_MIXED(TA, TV)                                        \
-    template void dilu_fwd_b4<TA, TV>(const int*, const int*, const TA*,      \
-                                      const TA*, const int*, int, const TV*,  \
-                                      TV*, hipStream_t);                      \
-    template void dilu_bwd_b4<TA, TV>(const int*, const int*, const TA*,      \
-                                      const TA*, const int*, int, const TV*,  \
-                                      TV*, hipStream_t);                      \
     template void dilu_fwd_b4_sorted<TA, TV>(const int*, const int*,          \
-                                             const TA*, const TA*,           \
+                                             const TA*, const TA*,            \
                                              const int*, int, const TV*,      \
-                                             TV*, hipStream_t);               \
-    template void dilu_fwd_b4_sorted_fused<TA, TV>(const int*, const int*,    \
-                                                   const TA*, const TA*,      \
-                                                   const int*, int,           \
-                                                   const TV*, const TV*,      \
-                                                   TV*, hipStream_t);         \
+                                             const TV*, TV*, hipStream_t);    \
     template void dilu_bwd_b4_sorted<TA, TV>(const int*, const int*,          \
-                                             const TA*, const TA*,           \
+                                             const TA*, const TA*,            \
                                              const int*, int, const TV*,      \
                                              TV*, hipStream_t);               \
     template void bsrmv_b4<TA, TV>(const int*, const int*, const TA*,         \

@@ -489,6 +489,31 @@ void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
     }
 }
 
+// ============================================================ multicolor sweeps
+// Row product of slot t of a color-sorted slab with the gathered vector v
+// (FUSED: with xres + v, which folds a residual into the product). The
+// first 8 entries are peeled so their loads issue together; summation
+// runs in ascending k.
+template <bool FUSED, typename TA, typename TV>
+__device__ __forceinline__ TV slab_row_dot(const int* __restrict__ ro_s,
+                                           const int* __restrict__ ci_s,
+                                           const TA* __restrict__ va_s, int t,
+                                           const TV* v,
+                                           const TV* xres = nullptr) {
+    auto term = [&](int k) {
+        int j = ci_s[k];
+        return (TV)va_s[k] * (FUSED ? xres[j] + v[j] : v[j]);
+    };
+    int k = ro_s[t], e = ro_s[t + 1];
+    TV sum = TV(0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        if (k < e) { sum += term(k); ++k; }
+    }
+    for (; k < e; ++k) sum += term(k);
+    return sum;
+}
+
 // ============================================================ multicolor GS
 // color-sorted GS row sweep (reorder-by-color layout; ro_s/rows/dinv_s
 // pre-offset to the color base, matrix arrays gathered in rows_sorted
@@ -502,13 +527,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void gs_rows_scalar_sorted(
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    int k = ro_s[t], e = ro_s[t + 1];
-    TV sum = TV(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (k < e) { sum += (TV)va_s[k] * x[ci_s[k]]; ++k; }
-    }
-    for (; k < e; ++k) sum += (TV)va_s[k] * x[ci_s[k]];
+    TV sum = slab_row_dot<false>(ro_s, ci_s, va_s, t, x);
     x[i] += omega * (TV)dinv_s[t] * (bvec[i] - sum);
 }
 
@@ -737,215 +756,35 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
     }
 }
 
-// forward: w_i = Einv_i (r_i - sum_{color(j)<c} A_ij w_j); w pre-zeroed so the
-// full-row product only picks up earlier colors (valid coloring => no
-// same-color off-diagonals; diagonal contributes w_i = 0).
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar(const int* __restrict__ ro,
-                                const int* __restrict__ ci,
-                                const TA* __restrict__ va,
-                                const TA* __restrict__ einv,
-                                const int* __restrict__ rows, int count,
-                                const TV* __restrict__ r, TV* __restrict__ w) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    TV sum = TV(0);
-    for (int k = ro[i]; k < ro[i + 1]; ++k) sum += (TV)va[k] * w[ci[k]];
-    w[i] = (TV)einv[i] * (r[i] - sum);
-}
-
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_block(const int* __restrict__ ro,
-                               const int* __restrict__ ci,
-                               const TA* __restrict__ va,
-                               const TA* __restrict__ einv,
-                               const int* __restrict__ rows, int count,
-                               const TV* __restrict__ r, TV* __restrict__ w,
-                               int b) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    TV acc[16];           // b <= 16
-    for (int c = 0; c < b; ++c) {
-        TV sum = TV(0);
-        for (int k = ro[i]; k < ro[i + 1]; ++k) {
-            if (ci[k] == i) continue;
-            const TA* blk = va + ((long long)k * b + c) * b;
-            const TV* ws = w + (long long)ci[k] * b;
-            for (int q = 0; q < b; ++q) sum += (TV)blk[q] * ws[q];
-        }
-        acc[c] = r[(long long)i * b + c] - sum;
-    }
-    const TA* E = einv + (long long)i * b * b;
-    for (int c = 0; c < b; ++c) {
-        TV s = TV(0);
-        for (int q = 0; q < b; ++q) s += (TV)E[c * b + q] * acc[q];
-        w[(long long)i * b + c] = s;
-    }
-}
-
-// backward: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j; z pre-zeroed and
-// filled color-descending, so a full-row product sees only later colors.
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar(const int* __restrict__ ro,
-                                const int* __restrict__ ci,
-                                const TA* __restrict__ va,
-                                const TA* __restrict__ einv,
-                                const int* __restrict__ rows, int count,
-                                const TV* __restrict__ w, TV* __restrict__ z) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    TV sum = TV(0);
-    for (int k = ro[i]; k < ro[i + 1]; ++k) sum += (TV)va[k] * z[ci[k]];
-    z[i] = w[i] - (TV)einv[i] * sum;
-}
-
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_block(const int* __restrict__ ro,
-                               const int* __restrict__ ci,
-                               const TA* __restrict__ va,
-                               const TA* __restrict__ einv,
-                               const int* __restrict__ rows, int count,
-                               const TV* __restrict__ w, TV* __restrict__ z,
-                               int b) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    TV acc[16];           // b <= 16
-    for (int c = 0; c < b; ++c) {
-        TV sum = TV(0);
-        for (int k = ro[i]; k < ro[i + 1]; ++k) {
-            if (ci[k] == i) continue;
-            const TA* blk = va + ((long long)k * b + c) * b;
-            const TV* zs = z + (long long)ci[k] * b;
-            for (int q = 0; q < b; ++q) sum += (TV)blk[q] * zs[q];
-        }
-        acc[c] = sum;
-    }
-    const TA* E = einv + (long long)i * b * b;
-    for (int c = 0; c < b; ++c) {
-        TV s = TV(0);
-        for (int q = 0; q < b; ++q) s += (TV)E[c * b + q] * acc[q];
-        z[(long long)i * b + c] = w[(long long)i * b + c] - s;
-    }
-}
-
 // ---- color-sorted sweep variants (reference reorder-by-color layout,
 // include/matrix.h:766, src/core.cu:489-506, redesigned as a sorted COPY):
 // the matrix rows are stored in rows_sorted order, so each color's sweep
 // reads a CONTIGUOUS slab of values/columns exactly once — the original
 // per-color launches re-fetched ~num_colors scattered cache lines per
 // sweep.  ro_s/rows/einv_s pointers arrive pre-offset to the color base.
-template <typename TA, typename TV>
+//
+// forward: w_i = Einv_i (rhs_i - sum_{color(j)<c} A_ij w_j); w pre-zeroed so
+// the full-row product only picks up earlier colors (valid coloring => no
+// same-color off-diagonals; diagonal contributes w_i = 0).
+// FUSED folds the residual into the sweep: w_i = Einv_i (b_i - sum_k a_k
+// (x_k + w_k)).  The single gather x[j]+w[j] replaces residual kernel +
+// sweep with one matrix read, mathematically identical to r = b - A x;
+// M w = r.
+template <typename TA, typename TV, bool FUSED>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_sorted(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
     const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ r,
-    TV* __restrict__ w) {
+    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
+    const TV* __restrict__ xres, TV* __restrict__ w) {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    int k = ro_s[t], e = ro_s[t + 1];
-    TV sum = TV(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (k < e) { sum += (TV)va_s[k] * w[ci_s[k]]; ++k; }
-    }
-    for (; k < e; ++k) sum += (TV)va_s[k] * w[ci_s[k]];
-    w[i] = (TV)einv_s[t] * (r[i] - sum);
+    TV sum = slab_row_dot<FUSED>(ro_s, ci_s, va_s, t, w, xres);
+    w[i] = (TV)einv_s[t] * (rhs[i] - sum);
 }
 
-// fused-residual forward sweep: w_i = Einv_i (b_i - sum_k a_k (x_k + w_k)).
-// Since w is pre-zeroed and only earlier colors are filled, the single
-// gather x[j]+w[j] folds the residual b-Ax INTO the substitution — one
-// matrix read instead of two (residual kernel + sweep), mathematically
-// identical to r = b - A x; M w = r.
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_sorted_fused(
-    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
-    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ bvec,
-    const TV* __restrict__ x, TV* __restrict__ w) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    int i = rows[t];
-    int k = ro_s[t], e = ro_s[t + 1];
-    TV sum = TV(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (k < e) { int j = ci_s[k];
-                     sum += (TV)va_s[k] * (x[j] + w[j]); ++k; }
-    }
-    for (; k < e; ++k) {
-        int j = ci_s[k];
-        sum += (TV)va_s[k] * (x[j] + w[j]);
-    }
-    w[i] = (TV)einv_s[t] * (bvec[i] - sum);
-}
-
-template <typename TA, typename TV>
-void dilu_fwd_sorted_fused(const int* ro_s, const int* ci_s, const TA* va_s,
-                           const TA* einv_s, const int* rows, int count,
-                           const TV* bvec, const TV* x, TV* w,
-                           hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_fwd_scalar_sorted_fused<TA, TV>),
-                       dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s, ro_s,
-                       ci_s, va_s, einv_s, rows, count, bvec, x, w);
-}
-
-// whole-apply fused-residual kernel for small levels (cf. dilu_apply_small)
-template <typename TA, typename TV>
-__global__ __launch_bounds__(1024) void dilu_smooth_small_kernel(
-    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
-    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, const int* __restrict__ bounds,
-    int ncolors, const TV* __restrict__ bvec, TV* __restrict__ w,
-    TV* __restrict__ z, TV* __restrict__ x, TV relax, long long vec_n) {
-    int tid = threadIdx.x;
-    int nt = blockDim.x;
-    for (long long i = tid; i < vec_n; i += nt) { w[i] = TV(0); z[i] = TV(0); }
-    __syncthreads();
-    for (int c = 0; c < ncolors; ++c) {
-        int s0 = bounds[c], s1 = bounds[c + 1];
-        for (int t = s0 + tid; t < s1; t += nt) {
-            int i = rows[t];
-            TV sum = TV(0);
-            for (int k = ro_s[t]; k < ro_s[t + 1]; ++k) {
-                int j = ci_s[k];
-                sum += (TV)va_s[k] * (x[j] + w[j]);
-            }
-            w[i] = (TV)einv_s[t] * (bvec[i] - sum);
-        }
-        __syncthreads();
-    }
-    for (int c = ncolors - 1; c >= 0; --c) {
-        int s0 = bounds[c], s1 = bounds[c + 1];
-        for (int t = s0 + tid; t < s1; t += nt) {
-            int i = rows[t];
-            TV sum = TV(0);
-            for (int k = ro_s[t]; k < ro_s[t + 1]; ++k)
-                sum += (TV)va_s[k] * z[ci_s[k]];
-            z[i] = w[i] - (TV)einv_s[t] * sum;
-        }
-        __syncthreads();
-    }
-    long long xn = (long long)bounds[ncolors];
-    for (long long i = tid; i < xn; i += nt) x[i] += relax * z[i];
-}
-
-template <typename TA, typename TV>
-void dilu_smooth_small(const int* ro_s, const int* ci_s, const TA* va_s,
-                       const TA* einv_s, const int* rows, const int* bounds,
-                       int ncolors, const TV* bvec, TV* w, TV* z, TV* x,
-                       TV relax, long long vec_n, hipStream_t s) {
-    hipLaunchKernelGGL((dilu_smooth_small_kernel<TA, TV>), dim3(1),
-                       dim3(1024), 0, s, ro_s, ci_s, va_s, einv_s, rows,
-                       bounds, ncolors, bvec, w, z, x, relax, vec_n);
-}
-
+// backward: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j; z pre-zeroed and
+// filled color-descending, so a full-row product sees only later colors.
 template <typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_sorted(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
@@ -955,13 +794,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_sorted(
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    int k = ro_s[t], e = ro_s[t + 1];
-    TV sum = TV(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (k < e) { sum += (TV)va_s[k] * z[ci_s[k]]; ++k; }
-    }
-    for (; k < e; ++k) sum += (TV)va_s[k] * z[ci_s[k]];
+    TV sum = slab_row_dot<false>(ro_s, ci_s, va_s, t, z);
     z[i] = wv[i] - (TV)einv_s[t] * sum;
 }
 
@@ -1027,12 +860,13 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_block_sorted(
 // barrier.  The per-color launch floor (~5-20us x ncolors x 2 sweeps x
 // sweeps-per-smooth x ~15 coarse levels) dominated the V-cycle before
 // this (rocprof r02: 95k launches, 2.0 of 3.0 s GPU time at 192^3).
-template <typename TA, typename TV>
-__global__ __launch_bounds__(1024) void dilu_apply_small_kernel(
+// FUSED: rhs is b and the forward gather is x[j]+w[j] (fused residual).
+template <typename TA, typename TV, bool FUSED>
+__global__ __launch_bounds__(1024) void dilu_small_kernel(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
     const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
     const int* __restrict__ rows, const int* __restrict__ bounds,
-    int ncolors, const TV* __restrict__ r, TV* __restrict__ w,
+    int ncolors, const TV* __restrict__ rhs, TV* __restrict__ w,
     TV* __restrict__ z, TV* __restrict__ x, TV relax, long long vec_n) {
     int tid = threadIdx.x;
     int nt = blockDim.x;
@@ -1043,9 +877,11 @@ __global__ __launch_bounds__(1024) void dilu_apply_small_kernel(
         for (int t = s0 + tid; t < s1; t += nt) {
             int i = rows[t];
             TV sum = TV(0);
-            for (int k = ro_s[t]; k < ro_s[t + 1]; ++k)
-                sum += (TV)va_s[k] * w[ci_s[k]];
-            w[i] = (TV)einv_s[t] * (r[i] - sum);
+            for (int k = ro_s[t]; k < ro_s[t + 1]; ++k) {
+                int j = ci_s[k];
+                sum += (TV)va_s[k] * (FUSED ? x[j] + w[j] : w[j]);
+            }
+            w[i] = (TV)einv_s[t] * (rhs[i] - sum);
         }
         __syncthreads();
     }
@@ -1065,31 +901,39 @@ __global__ __launch_bounds__(1024) void dilu_apply_small_kernel(
 }
 
 template <typename TA, typename TV>
-void dilu_apply_small(const int* ro_s, const int* ci_s, const TA* va_s,
-                      const TA* einv_s, const int* rows, const int* bounds,
-                      int ncolors, const TV* r, TV* w, TV* z, TV* x,
-                      TV relax, long long vec_n, hipStream_t s) {
-    hipLaunchKernelGGL((dilu_apply_small_kernel<TA, TV>), dim3(1),
-                       dim3(1024), 0, s, ro_s, ci_s, va_s, einv_s, rows,
-                       bounds, ncolors, r, w, z, x, relax, vec_n);
+void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
+                const TA* einv_s, const int* rows, const int* bounds,
+                int ncolors, const TV* rhs, TV* w, TV* z, TV* x, TV relax,
+                long long vec_n, bool fused, hipStream_t s) {
+    auto kern = fused ? dilu_small_kernel<TA, TV, true>
+                      : dilu_small_kernel<TA, TV, false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, s, ro_s, ci_s, va_s,
+                       einv_s, rows, bounds, ncolors, rhs, w, z, x, relax,
+                       vec_n);
 }
 
+// xres != nullptr selects the fused-residual sweep (rhs = b, xres = x);
+// there is no fused kernel for generic block sizes (caller guards)
 template <typename TA, typename TV>
 void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
-                     const TV* r, TV* w, int b, hipStream_t s) {
+                     const TV* rhs, const TV* xres, TV* w, int b,
+                     hipStream_t s) {
     if (count <= 0) return;
-    if (b == 1)
-        hipLaunchKernelGGL((dilu_fwd_scalar_sorted<TA, TV>),
-                           dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
-                           ro_s, ci_s, va_s, einv_s, rows, count, r, w);
-    else if (b == 4)       // MFMA wave kernel (kernels_mfma.hip)
-        dilu_fwd_b4_sorted<TA, TV>(ro_s, ci_s, va_s, einv_s, rows, count, r,
-                                   w, s);
-    else
+    if (b == 1) {
+        auto kern = xres ? dilu_fwd_scalar_sorted<TA, TV, true>
+                         : dilu_fwd_scalar_sorted<TA, TV, false>;
+        hipLaunchKernelGGL(kern, dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0,
+                           s, ro_s, ci_s, va_s, einv_s, rows, count, rhs,
+                           xres, w);
+    } else if (b == 4) {   // MFMA wave kernel (kernels_mfma.hip)
+        dilu_fwd_b4_sorted<TA, TV>(ro_s, ci_s, va_s, einv_s, rows, count,
+                                   rhs, xres, w, s);
+    } else {
         hipLaunchKernelGGL((dilu_fwd_block_sorted<TA, TV>),
                            dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
-                           ro_s, ci_s, va_s, einv_s, rows, count, r, w, b);
+                           ro_s, ci_s, va_s, einv_s, rows, count, rhs, w, b);
+    }
 }
 
 template <typename TA, typename TV>
@@ -1108,42 +952,6 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
         hipLaunchKernelGGL((dilu_bwd_block_sorted<TA, TV>),
                            dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
                            ro_s, ci_s, va_s, einv_s, rows, count, wv, z, b);
-}
-
-template <typename TA, typename TV>
-void dilu_fwd_color(const int* ro, const int* ci, const TA* va,
-                    const TA* einv, const int* colors, const int* rows,
-                    int count, int color, const TV* r, TV* w, int b,
-                    hipStream_t s) {
-    if (count <= 0) return;
-    if (b == 1)
-        hipLaunchKernelGGL((dilu_fwd_scalar<TA, TV>), dim3(grid_1d(count)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, einv, rows,
-                           count, r, w);
-    else if (b == 4)       // MFMA wave kernel (kernels_mfma.hip)
-        dilu_fwd_b4<TA, TV>(ro, ci, va, einv, rows, count, r, w, s);
-    else
-        hipLaunchKernelGGL((dilu_fwd_block<TA, TV>), dim3(grid_1d(count)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, einv, rows,
-                           count, r, w, b);
-}
-
-template <typename TA, typename TV>
-void dilu_bwd_color(const int* ro, const int* ci, const TA* va,
-                    const TA* einv, const int* colors, const int* rows,
-                    int count, int color, const TV* w, TV* z, int b,
-                    hipStream_t s) {
-    if (count <= 0) return;
-    if (b == 1)
-        hipLaunchKernelGGL((dilu_bwd_scalar<TA, TV>), dim3(grid_1d(count)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, einv, rows,
-                           count, w, z);
-    else if (b == 4)       // MFMA wave kernel (kernels_mfma.hip)
-        dilu_bwd_b4<TA, TV>(ro, ci, va, einv, rows, count, w, z, s);
-    else
-        hipLaunchKernelGGL((dilu_bwd_block<TA, TV>), dim3(grid_1d(count)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, einv, rows,
-                           count, w, z, b);
 }
 
 // ============================================================ transfers
@@ -1243,7 +1051,7 @@ void dense_gemv(const TA* Ainv, const TV* b, TV* x, int n, hipStream_t s) {
                        0, s, Ainv, b, x, n);
 }
 
-// ============================================================ gather/scatter
+// ============================================================ gather
 template <typename T>
 __global__ __launch_bounds__(AMGX_BLOCK) void gather_kernel(const T* __restrict__ src,
                               const int* __restrict__ idx, long long count,
@@ -1256,44 +1064,12 @@ __global__ __launch_bounds__(AMGX_BLOCK) void gather_kernel(const T* __restrict_
 }
 
 template <typename T>
-__global__ __launch_bounds__(AMGX_BLOCK) void scatter_kernel(const T* __restrict__ src,
-                               const int* __restrict__ idx, long long count,
-                               int b, T* __restrict__ dst, bool add) {
-    long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count * b) return;
-    long long i = t / b;
-    int c = (int)(t % b);
-    if (add)
-        atomicAdd(&dst[(long long)idx[i] * b + c], src[t]);
-    else
-        dst[(long long)idx[i] * b + c] = src[t];
-}
-
-template <typename T>
 void gather(const T* src, const int* idx, int count, int b, T* dst,
             hipStream_t s) {
     if (count <= 0) return;
     hipLaunchKernelGGL((gather_kernel<T>),
                        dim3(grid_1d((long long)count * b)), dim3(AMGX_BLOCK),
                        0, s, src, idx, (long long)count, b, dst);
-}
-
-template <typename T>
-void scatter(const T* src, const int* idx, int count, int b, T* dst,
-             hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((scatter_kernel<T>),
-                       dim3(grid_1d((long long)count * b)), dim3(AMGX_BLOCK),
-                       0, s, src, idx, (long long)count, b, dst, false);
-}
-
-template <typename T>
-void scatter_add(const T* src, const int* idx, int count, int b, T* dst,
-                 hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL((scatter_kernel<T>),
-                       dim3(grid_1d((long long)count * b)), dim3(AMGX_BLOCK),
-                       0, s, src, idx, (long long)count, b, dst, true);
 }
 
 // ============================================================ instantiation
@@ -1321,10 +1097,7 @@ void scatter_add(const T* src, const int* idx, int count, int b, T* dst,
                                   T*, hipStream_t);                             \
     template void prolongate_agg<T>(T*, const T*, const int*, int, int,         \
                                     hipStream_t);                               \
-    template void gather<T>(const T*, const int*, int, int, T*, hipStream_t);   \
-    template void scatter<T>(const T*, const int*, int, int, T*, hipStream_t);  \
-    template void scatter_add<T>(const T*, const int*, int, int, T*,            \
-                                 hipStream_t);
+    template void gather<T>(const T*, const int*, int, int, T*, hipStream_t);
 
 // matrix-value x vector mixed ops: (TA, TV) in {(d,d), (f,f), (f,d)} — the
 // reference's dDDI / dFFI / dDFI value modes
@@ -1341,23 +1114,14 @@ void scatter_add(const T* src, const int* idx, int count, int b, T* dst,
     template void jacobi_smooth<TA, TV>(const int*, const int*, const TA*,      \
                                         const TA*, const TV*, const TV*, TV*,   \
                                         TV, int, int, double, hipStream_t);     \
-    template void dilu_fwd_sorted_fused<TA, TV>(const int*, const int*,         \
-                                                const TA*, const TA*,           \
-                                                const int*, int, const TV*,     \
-                                                const TV*, TV*, hipStream_t);   \
-    template void dilu_smooth_small<TA, TV>(const int*, const int*,             \
-                                            const TA*, const TA*, const int*,   \
-                                            const int*, int, const TV*, TV*,    \
-                                            TV*, TV*, TV, long long,            \
-                                            hipStream_t);                       \
-    template void dilu_apply_small<TA, TV>(const int*, const int*,              \
-                                           const TA*, const TA*, const int*,    \
-                                           const int*, int, const TV*, TV*,     \
-                                           TV*, TV*, TV, long long,             \
-                                           hipStream_t);                        \
+    template void dilu_small<TA, TV>(const int*, const int*, const TA*,         \
+                                     const TA*, const int*, const int*, int,    \
+                                     const TV*, TV*, TV*, TV*, TV, long long,   \
+                                     bool, hipStream_t);                        \
     template void dilu_fwd_sorted<TA, TV>(const int*, const int*, const TA*,    \
                                           const TA*, const int*, int,           \
-                                          const TV*, TV*, int, hipStream_t);    \
+                                          const TV*, const TV*, TV*, int,       \
+                                          hipStream_t);                         \
     template void dilu_bwd_sorted<TA, TV>(const int*, const int*, const TA*,    \
                                           const TA*, const int*, int,           \
                                           const TV*, TV*, int, hipStream_t);    \
@@ -1371,14 +1135,6 @@ void scatter_add(const T* src, const int* idx, int count, int b, T* dst,
     template void gs_smooth_rows<TA, TV>(const int*, const int*, const TA*,     \
                                          const TA*, const TV*, TV*,             \
                                          const int*, int, TV, int, int,         \
-                                         hipStream_t);                          \
-    template void dilu_fwd_color<TA, TV>(const int*, const int*, const TA*,     \
-                                         const TA*, const int*, const int*,     \
-                                         int, int, const TV*, TV*, int,         \
-                                         hipStream_t);                          \
-    template void dilu_bwd_color<TA, TV>(const int*, const int*, const TA*,     \
-                                         const TA*, const int*, const int*,     \
-                                         int, int, const TV*, TV*, int,         \
                                          hipStream_t);                          \
     template void dense_gemv<TA, TV>(const TA*, const TV*, TV*, int,            \
                                      hipStream_t);

@@ -163,21 +163,13 @@ def gs_smooth_color(A, dinv, b, x, color_rows, omega: float):
 def gs_sweep(A, dinv, b, x, coloring, omega: float, symmetric: bool = False):
     if A.block_dim == 1:
         # color-sorted slab layout (reference reorder-by-color)
-        ro_s, ci_s, pos, perm = _color_sorted_struct(A, coloring)
-        vkey = ("gs_va_s", id(coloring), A.values._version)
-        va_s = A._cache.get(vkey)
-        if va_s is None:
-            va_s = A.values[pos].contiguous()
-            A._cache[vkey] = va_s
-        dkey = ("gs_dinv_s", id(coloring), dinv._version, dinv.data_ptr())
-        dinv_s = A._cache.get(dkey)
-        if dinv_s is None:
-            dinv_s = dinv.reshape(-1)[perm].contiguous()
-            A._cache[dkey] = dinv_s
-        _core.gs_sweep_sorted(ro_s, ci_s, va_s, dinv_s, b.reshape(-1),
+        st = _slabs(A, coloring)
+        va_s = _slab_copy(st, "gs_va", A.values, lambda v: v[st.nzmap])
+        dinv_s = _slab_copy(st, "gs_dinv", dinv,
+                            lambda d: d.reshape(-1)[st.perm])
+        _core.gs_sweep_sorted(st.ro_s, st.ci_s, va_s, dinv_s, b.reshape(-1),
                               x.reshape(-1), coloring.rows_sorted,
-                              coloring.bounds,
-                              getattr(coloring, "bounds_dev", None),
+                              coloring.bounds, coloring.bounds_dev,
                               float(omega), bool(symmetric))
         return x
     _core.gs_sweep(A.row_offsets, A.col_indices, A.values, A.block_dim, dinv,
@@ -199,29 +191,54 @@ def color_matrix(A, max_uncolored_frac: float = 0.0, seed: int = 0,
 
 
 # ---------------------------------------------------------------------- DILU
-def _color_sorted_struct(A, coloring):
-    """Structure of the rows_sorted-gathered matrix copy (reference
-    reorder-by-color, include/matrix.h:766): slot-ordered row offsets,
-    gathered columns, and the nz gather map (for value re-gathers after
-    replace_coefficients). Cached per (matrix, coloring)."""
-    key = ("csorted", id(coloring))
-    st = A._cache.get(key)
-    if st is None:
+class _Slabs:
+    """Structure of the rows_sorted-gathered matrix copy under ONE coloring
+    (reference reorder-by-color, include/matrix.h:766): slot-ordered row
+    offsets ro_s, gathered columns ci_s, the nz gather map nzmap (for value
+    re-gathers after replace_coefficients), perm = rows_sorted as int64 and
+    its inverse slot_of_row; copies holds the gathered value arrays."""
+    __slots__ = ("coloring", "ro_s", "ci_s", "nzmap", "perm", "slot_of_row",
+                 "copies")
+
+
+def _slabs(A, coloring):
+    """The matrix's slab record; rebuilt (dropping every gathered copy) when
+    the matrix is swept under another coloring object."""
+    st = A._cache.get("slabs")
+    if st is None or st.coloring is not coloring:
+        st = _Slabs()
+        st.coloring = coloring
+        st.copies = {}
+        n = A.n_rows
         perm = coloring.rows_sorted.to(torch.int64)
         ro64 = A.row_offsets.to(torch.int64)
         deg = ro64[1:] - ro64[:-1]
         counts = deg[perm]
         total = int(A.nnz)
-        ro_s = torch.zeros(A.n_rows + 1, dtype=torch.int32, device=A.device)
+        st.ro_s = torch.zeros(n + 1, dtype=torch.int32, device=A.device)
         csum = torch.cumsum(counts, 0)
-        ro_s[1:] = csum.to(torch.int32)
-        pos = (torch.repeat_interleave(ro64[perm], counts)
-               + torch.arange(total, device=A.device, dtype=torch.int64)
-               - torch.repeat_interleave(csum - counts, counts))
-        ci_s = A.col_indices[pos].contiguous()
-        st = (ro_s, ci_s, pos, perm)
-        A._cache[key] = st
+        st.ro_s[1:] = csum.to(torch.int32)
+        st.nzmap = (torch.repeat_interleave(ro64[perm], counts)
+                    + torch.arange(total, device=A.device, dtype=torch.int64)
+                    - torch.repeat_interleave(csum - counts, counts))
+        st.ci_s = A.col_indices[st.nzmap].contiguous()
+        st.perm = perm
+        st.slot_of_row = torch.empty(n, dtype=torch.int32, device=A.device)
+        st.slot_of_row[perm] = torch.arange(n, dtype=torch.int32,
+                                            device=A.device)
+        A._cache["slabs"] = st
     return st
+
+
+def _slab_copy(st, name, src, gather):
+    """gather(src) in slab order, redone when src is another tensor or has
+    been written in place since the cached copy was taken."""
+    key = (src.data_ptr(), src._version)
+    hit = st.copies.get(name)
+    if hit is None or hit[0] != key:
+        hit = (key, gather(src))
+        st.copies[name] = hit
+    return hit[1]
 
 
 class DiluState:
@@ -242,12 +259,23 @@ def dilu_setup(A, coloring):
     einv = _core.dilu_setup(A.row_offsets, A.col_indices, A.values,
                             A.block_dim, _didx(A), _tidx(A), coloring.colors,
                             coloring.rows_sorted, coloring.bounds)
-    ro_s, ci_s, pos, perm = _color_sorted_struct(A, coloring)
+    st = _slabs(A, coloring)
     bb = A.block_dim * A.block_dim
-    va_s = A.values.reshape(A.nnz, -1)[pos].reshape(-1).contiguous()
-    einv_s = einv.reshape(A.n_rows, bb)[perm].reshape(-1).contiguous() \
-        if A.block_dim > 1 else einv[perm].contiguous()
+    va_s = A.values.reshape(A.nnz, -1)[st.nzmap].reshape(-1).contiguous()
+    einv_s = einv.reshape(A.n_rows, bb)[st.perm].reshape(-1).contiguous() \
+        if A.block_dim > 1 else einv[st.perm].contiguous()
     return DiluState(einv, va_s, einv_s)
+
+
+def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused):
+    n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
+    w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
+    z = _scratch(A, "dilu_z", n, x.dtype)
+    st = _slabs(A, coloring)
+    _core.dilu_sorted(st.ro_s, st.ci_s, Einv.va_s, A.block_dim, Einv.einv_s,
+                      coloring.rows_sorted, coloring.bounds,
+                      coloring.bounds_dev, rhs.reshape(-1), w, z,
+                      x.reshape(-1), float(relaxation), fused)
 
 
 def dilu_smooth(A, Einv, coloring, b, x, relaxation):
@@ -255,40 +283,16 @@ def dilu_smooth(A, Einv, coloring, b, x, relaxation):
     forward sweep (one matrix read fewer than residual + dilu_solve);
     b=1 scalar and b=4 MFMA paths. Returns False when this block size has
     no fused kernel (caller falls back to residual + dilu_solve)."""
-    if not isinstance(Einv, DiluState) or A.block_dim not in (1, 4):
+    if A.block_dim not in (1, 4):
         return False
     if getattr(A, "manager", None) is not None:
         return False   # distributed path must exchange halos of x first
-    n = A.n_cols * A.block_dim
-    w = _scratch(A, "dilu_w", n, x.dtype)
-    z = _scratch(A, "dilu_z", n, x.dtype)
-    ro_s, ci_s, pos, perm = _color_sorted_struct(A, coloring)
-    _core.dilu_smooth_sorted(ro_s, ci_s, Einv.va_s, A.block_dim,
-                             Einv.einv_s, coloring.rows_sorted,
-                             coloring.bounds,
-                             getattr(coloring, "bounds_dev", None),
-                             b.reshape(-1), x.reshape(-1), w, z,
-                             float(relaxation))
+    _dilu_sorted(A, Einv, coloring, b, x, relaxation, True)
     return True
 
 
 def dilu_solve(A, Einv, coloring, r, relaxation, x):
-    n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
-    w = _scratch(A, "dilu_w", n, r.dtype)   # vector precision (dDFI mixed)
-    z = _scratch(A, "dilu_z", n, r.dtype)
-    if isinstance(Einv, DiluState):
-        ro_s, ci_s, pos, perm = _color_sorted_struct(A, coloring)
-        _core.dilu_apply_sorted(ro_s, ci_s, Einv.va_s, A.block_dim,
-                                Einv.einv_s, coloring.rows_sorted,
-                                coloring.bounds,
-                                getattr(coloring, "bounds_dev", None),
-                                r.reshape(-1), w, z,
-                                x.reshape(-1), float(relaxation))
-        return x
-    _core.dilu_apply(A.row_offsets, A.col_indices, A.values, A.block_dim,
-                     Einv, coloring.colors, coloring.rows_sorted,
-                     coloring.bounds, r.reshape(-1), w, z, x.reshape(-1),
-                     float(relaxation))
+    _dilu_sorted(A, Einv, coloring, r, x, relaxation, False)
     return x
 
 
@@ -471,20 +475,8 @@ def interp_d1(A, S, cf_map, num_coarse):
 
 
 # ---------------------------------------------------------------------- ILU(0)
-def _color_pos(A, coloring):
-    key = "ilu_pos"
-    pos = A._cache.get(key)
-    if pos is None:
-        n = A.n_rows
-        pos = torch.empty(n, dtype=torch.int32, device=A.device)
-        pos[coloring.rows_sorted.to(torch.int64)] = \
-            torch.arange(n, dtype=torch.int32, device=A.device)
-        A._cache[key] = pos
-    return pos
-
-
 def ilu0_setup(A, coloring):
-    pos = _color_pos(A, coloring)
+    pos = _slabs(A, coloring).slot_of_row
     if A.block_dim != 1:
         lu, dinv = _core.ilu0_setup_block(
             A.row_offsets, A.col_indices, A.values.reshape(-1), A.block_dim,
@@ -499,26 +491,21 @@ def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):
     n = A.n_cols * A.block_dim
     y = _scratch(A, "ilu_y", n, r.dtype)    # vector precision (dDFI mixed)
     z = _scratch(A, "ilu_z", n, r.dtype)
-    pos = _color_pos(A, coloring)
+    st = _slabs(A, coloring)
     if A.block_dim != 1:
         lu, dinv = factors
         _core.ilu0_apply_block(A.row_offsets, A.col_indices, lu, dinv,
-                               A.block_dim, pos, coloring.rows_sorted,
-                               coloring.bounds, r.reshape(-1), y, z,
-                               x.reshape(-1), float(relaxation))
+                               A.block_dim, st.slot_of_row,
+                               coloring.rows_sorted, coloring.bounds,
+                               r.reshape(-1), y, z, x.reshape(-1),
+                               float(relaxation))
         return x
     # color-sorted slabs (same layout win as the DILU sweeps)
-    ro_s, ci_s, nzpos, perm = _color_sorted_struct(A, coloring)
-    lkey = ("ilu_lu_s", id(coloring), factors._version, factors.data_ptr())
-    cached = A._cache.get(lkey)
-    if cached is None:
-        lu_s = factors.reshape(-1)[nzpos].contiguous()
-        diag_s = factors.reshape(-1)[_didx(A).to(torch.int64)][perm] \
-            .contiguous()
-        A._cache[lkey] = (lu_s, diag_s)
-    else:
-        lu_s, diag_s = cached
-    _core.ilu0_apply_sorted(ro_s, ci_s, lu_s, diag_s, pos,
+    lu_s, diag_s = _slab_copy(
+        st, "ilu", factors, lambda f: (
+            f.reshape(-1)[st.nzmap],
+            f.reshape(-1)[_didx(A).to(torch.int64)][st.perm]))
+    _core.ilu0_apply_sorted(st.ro_s, st.ci_s, lu_s, diag_s, st.slot_of_row,
                             coloring.rows_sorted, coloring.bounds,
                             r.reshape(-1), y, z, x.reshape(-1),
                             float(relaxation))

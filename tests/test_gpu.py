@@ -977,3 +977,186 @@ def test_coarse_generators_agree():
     assert torch.equal(C1.row_offsets, C2.row_offsets)
     assert torch.equal(C1.col_indices, C2.col_indices)
     assert torch.allclose(C1.values, C2.values, atol=1e-12)
+
+
+# ---------------------------------------------------------------- sweeps
+def _cpu_coloring(colg):
+    return MatrixColoring(colg.colors.cpu(), colg.num_colors)
+
+
+def _cpu_dilu_smooth(A, einv, col, b, x, relax):
+    """CPU reference of the fused smoother: residual, then DILU apply."""
+    from amgx_amd.ops import cpu as cpu_ops
+    cpu_ops.dilu_solve(A, einv, col, cpu_ops.residual(A, x, b), relax, x)
+    return x
+
+
+@pytest.fixture(scope="module")
+def big_level():
+    """One scalar level just above the single-workgroup threshold, so the
+    sweeps take the one-launch-per-color kernels (the path of the fine
+    benchmark levels), with the CPU DILU / ILU(0) factors every test of that
+    path compares against. Nothing here is modified by the tests."""
+    from types import SimpleNamespace
+    from amgx_amd import _core
+    from amgx_amd.ops import cpu as cpu_ops
+    A = poisson_2d(129, 128)
+    assert A.n_rows > _core.SMALL_LEVEL_ROWS
+    Ag = to_gpu(A)
+    colg = MatrixColoring.create(Ag)
+    col = _cpu_coloring(colg)
+    g = torch.Generator().manual_seed(11)
+    return SimpleNamespace(
+        A=A, Ag=Ag, colg=colg, col=col,
+        b=torch.rand(A.n_rows, generator=g, dtype=torch.float64),
+        x0=torch.rand(A.n_rows, generator=g, dtype=torch.float64),
+        dinv=cpu_ops.jacobi_dinv(A),
+        einv=cpu_ops.dilu_setup(A, col),
+        lu=cpu_ops.ilu0_setup(A, col))
+
+
+@pytest.mark.parametrize("symmetric", [False, True])
+def test_gs_sweep_per_color_path(big_level, symmetric):
+    from amgx_amd.ops import cpu as cpu_ops
+    L = big_level
+    x1 = L.x0.clone()
+    x2 = L.x0.cuda()
+    cpu_ops.gs_sweep(L.A, L.dinv, L.b, x1, L.col, 1.0, symmetric)
+    ops.gs_sweep(L.Ag, ops.jacobi_dinv(L.Ag), L.b.cuda(), x2, L.colg, 1.0,
+                 symmetric)
+    print("max dev", (x2.cpu() - x1).abs().max().item())
+    assert torch.allclose(x2.cpu(), x1, rtol=1e-12, atol=1e-13)
+
+
+def test_dilu_per_color_path(big_level):
+    from amgx_amd.ops import cpu as cpu_ops
+    from amgx_amd.ops import gpu as gpu_ops
+    L = big_level
+    e_gpu = ops.dilu_setup(L.Ag, L.colg)
+    print("setup max dev", (e_gpu.cpu() - L.einv).abs().max().item())
+    assert torch.allclose(e_gpu.cpu(), L.einv, rtol=1e-12, atol=1e-13)
+    x1 = torch.zeros_like(L.b)
+    x2 = x1.cuda()
+    cpu_ops.dilu_solve(L.A, L.einv, L.col, L.b, 0.9, x1)
+    ops.dilu_solve(L.Ag, e_gpu, L.colg, L.b.cuda(), 0.9, x2)
+    print("solve max dev", (x2.cpu() - x1).abs().max().item())
+    assert torch.allclose(x2.cpu(), x1, rtol=1e-11, atol=1e-12)
+    # fused-residual smoother from a nonzero iterate
+    y1 = _cpu_dilu_smooth(L.A, L.einv, L.col, L.b, L.x0.clone(), 0.9)
+    y2 = L.x0.cuda()
+    assert gpu_ops.dilu_smooth(L.Ag, e_gpu, L.colg, L.b.cuda(), y2, 0.9) \
+        is True
+    print("smooth max dev", (y2.cpu() - y1).abs().max().item())
+    assert torch.allclose(y2.cpu(), y1, rtol=1e-11, atol=1e-12)
+
+
+def test_ilu0_per_color_path(big_level):
+    from amgx_amd.ops import cpu as cpu_ops
+    from amgx_amd.ops import gpu as gpu_ops
+    L = big_level
+    lu_gpu = gpu_ops.ilu0_setup(L.Ag, L.colg)
+    print("setup max dev", (lu_gpu.cpu() - L.lu).abs().max().item())
+    assert torch.allclose(lu_gpu.cpu(), L.lu, rtol=1e-12, atol=1e-13)
+    x1 = torch.zeros_like(L.b)
+    x2 = x1.cuda()
+    cpu_ops.ilu0_solve(L.A, L.lu, L.col, L.b, x1, 1.0)
+    gpu_ops.ilu0_solve(L.Ag, lu_gpu, L.colg, L.b.cuda(), x2, 1.0)
+    print("solve max dev", (x2.cpu() - x1).abs().max().item())
+    assert torch.allclose(x2.cpu(), x1, rtol=1e-11, atol=1e-12)
+
+
+def test_mixed_precision_per_color_path(big_level):
+    """fp32 matrix x fp64 vectors through the per-color GS and DILU kernels
+    against the fp64 CPU reference."""
+    from amgx_amd.ops import cpu as cpu_ops
+    L = big_level
+    A32g = CSRMatrix(L.A.row_offsets, L.A.col_indices,
+                     L.A.values.to(torch.float32),
+                     n_cols=L.A.n_cols).to("cuda:0")
+    x1 = torch.zeros_like(L.b)
+    x2 = x1.cuda()
+    cpu_ops.gs_sweep(L.A, L.dinv, L.b, x1, L.col, 1.0)
+    ops.gs_sweep(A32g, ops.jacobi_dinv(A32g), L.b.cuda(), x2, L.colg, 1.0)
+    print("gs max dev", (x2.cpu() - x1).abs().max().item())
+    assert x2.dtype == torch.float64
+    assert torch.allclose(x2.cpu(), x1, rtol=1e-4, atol=1e-5)
+    w1 = torch.zeros_like(L.b)
+    w2 = w1.cuda()
+    cpu_ops.dilu_solve(L.A, L.einv, L.col, L.b, 0.9, w1)
+    ops.dilu_solve(A32g, ops.dilu_setup(A32g, L.colg), L.colg, L.b.cuda(),
+                   0.9, w2)
+    print("dilu max dev", (w2.cpu() - w1).abs().max().item())
+    assert torch.allclose(w2.cpu(), w1, rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("make,rtol,atol", [
+    (lambda: poisson_2d(16, 16), 1e-11, 1e-12),
+    (lambda: block_laplacian(8, 8, block_dim=4), 1e-9, 1e-11),
+], ids=["scalar", "block4"])
+def test_dilu_smooth_small_levels(make, rtol, atol):
+    """Fused-residual smoother entry point against CPU residual + apply."""
+    from amgx_amd.ops import cpu as cpu_ops
+    from amgx_amd.ops import gpu as gpu_ops
+    A = make()
+    Ag = to_gpu(A)
+    colg = MatrixColoring.create(Ag)
+    col = _cpu_coloring(colg)
+    g = torch.Generator().manual_seed(5)
+    n = A.n_rows * A.block_dim
+    b = torch.rand(n, generator=g, dtype=torch.float64)
+    x1 = torch.rand(n, generator=g, dtype=torch.float64)
+    x2 = x1.cuda()
+    _cpu_dilu_smooth(A, cpu_ops.dilu_setup(A, col), col, b, x1, 0.9)
+    done = gpu_ops.dilu_smooth(Ag, ops.dilu_setup(Ag, colg), colg, b.cuda(),
+                               x2, 0.9)
+    assert done is True
+    print("max dev", (x2.cpu() - x1).abs().max().item())
+    assert torch.allclose(x2.cpu(), x1, rtol=rtol, atol=atol)
+
+
+@pytest.mark.parametrize("bd", [2, 3, 5])
+def test_dilu_generic_block_gpu(bd):
+    """Sorted block kernels for block sizes without a specialised path."""
+    A = block_laplacian(9, 7, block_dim=bd, seed=bd)
+    Ag = to_gpu(A)
+    colg = MatrixColoring.create(Ag)
+    col = _cpu_coloring(colg)
+    e_ref = ops.dilu_setup(A, col)
+    e_gpu = ops.dilu_setup(Ag, colg)
+    print("setup max dev", (e_gpu.cpu() - e_ref).abs().max().item())
+    assert torch.allclose(e_gpu.cpu(), e_ref, rtol=1e-9, atol=1e-11)
+    r = torch.rand(A.n_rows * bd, dtype=torch.float64)
+    x1 = torch.zeros_like(r)
+    x2 = x1.cuda()
+    ops.dilu_solve(A, e_ref, col, r, 1.0, x1)
+    ops.dilu_solve(Ag, e_gpu, colg, r.cuda(), 1.0, x2)
+    print("solve max dev", (x2.cpu() - x1).abs().max().item())
+    assert torch.allclose(x2.cpu(), x1, rtol=1e-9, atol=1e-11)
+
+
+def test_slab_cache_follows_coloring():
+    """A matrix swept under a second coloring must not serve slabs or
+    elimination positions of the first."""
+    from amgx_amd.ops import cpu as cpu_ops
+    from amgx_amd.ops import gpu as gpu_ops
+    A = poisson_2d(16, 16)
+    Ag = to_gpu(A)
+    c1 = MatrixColoring.create(Ag)
+    c2 = MatrixColoring(c1.num_colors - 1 - c1.colors, c1.num_colors)
+    assert c2.validate(Ag)
+    r = torch.rand(A.n_rows, dtype=torch.float64)
+    for colg in (c1, c2):
+        Ag.coloring = colg
+        col = _cpu_coloring(colg)
+        x1 = torch.zeros_like(r)
+        x2 = x1.cuda()
+        cpu_ops.dilu_solve(A, cpu_ops.dilu_setup(A, col), col, r, 0.9, x1)
+        gpu_ops.dilu_solve(Ag, gpu_ops.dilu_setup(Ag, colg), colg, r.cuda(),
+                           0.9, x2)
+        assert torch.allclose(x2.cpu(), x1, rtol=1e-11, atol=1e-12)
+        y1 = torch.zeros_like(r)
+        y2 = y1.cuda()
+        cpu_ops.ilu0_solve(A, cpu_ops.ilu0_setup(A, col), col, r, y1, 1.0)
+        gpu_ops.ilu0_solve(Ag, gpu_ops.ilu0_setup(Ag, colg), colg, r.cuda(),
+                           y2, 1.0)
+        assert torch.allclose(y2.cpu(), y1, rtol=1e-11, atol=1e-12)
