@@ -7,7 +7,10 @@
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <pybind11/complex.h>
 
+#include <complex>
+#include <type_traits>
 #include <vector>
 
 #include "core_api.h"
@@ -52,6 +55,85 @@ inline void check_dev(const Tensor& t) {
     TORCH_CHECK(t.is_cuda(), "amgx_amd._core requires device tensors");
 }
 
+// ---- complex modes (dZZI / dCCI / dZCI) ------------------------------------
+// Only the entries of the Krylov + Jacobi path dispatch through the *C
+// macros below; every other entry keeps the real-only dispatch and raises on
+// complex tensors.
+using amgx_hip::cplx;
+using cscalar = std::complex<double>;   // coefficient as it arrives from Python
+
+template <typename T> struct is_cplx : std::false_type {};
+template <typename R> struct is_cplx<cplx<R>> : std::true_type {};
+template <typename T> struct tensor_elem { using type = T; };
+template <typename R> struct tensor_elem<cplx<R>> { using type = c10::complex<R>; };
+static_assert(sizeof(cplx<float>) == sizeof(c10::complex<float>) &&
+              sizeof(cplx<double>) == sizeof(c10::complex<double>),
+              "cplx must overlay the tensor element");
+
+// typed data pointer; data_ptr<> checks the tensor dtype, so a tensor of
+// another dtype raises instead of being reinterpreted
+template <typename T>
+T* dptr(const Tensor& t) {
+    return reinterpret_cast<T*>(t.data_ptr<typename tensor_elem<T>::type>());
+}
+
+// coefficient in the kernel's scalar type; a real kernel takes no imaginary part
+template <typename T>
+T coef(cscalar a, const char* name) {
+    if constexpr (is_cplx<T>::value) {
+        return T((decltype(T::re))a.real(), (decltype(T::re))a.imag());
+    } else {
+        TORCH_CHECK(a.imag() == 0.0, name,
+                    ": complex coefficient on real tensors");
+        return (T)a.real();
+    }
+}
+
+#define DISPATCH_FTC(TENSOR, NAME, ...)                                      \
+    do {                                                                     \
+        auto _t = (TENSOR).scalar_type();                                    \
+        if (_t == torch::kFloat64) {                                         \
+            using scalar_t = double;                                         \
+            __VA_ARGS__();                                                   \
+        } else if (_t == torch::kFloat32) {                                  \
+            using scalar_t = float;                                          \
+            __VA_ARGS__();                                                   \
+        } else if (_t == torch::kComplexDouble) {                            \
+            using scalar_t = cplx<double>;                                   \
+            __VA_ARGS__();                                                   \
+        } else if (_t == torch::kComplexFloat) {                             \
+            using scalar_t = cplx<float>;                                    \
+            __VA_ARGS__();                                                   \
+        } else {                                                             \
+            TORCH_CHECK(false, NAME, ": unsupported dtype ", _t);            \
+        }                                                                    \
+    } while (0)
+
+// DISPATCH_FT2 plus the complex pairs (Z,Z), (C,C), (C,Z). Complex x real,
+// real x complex and Z x C stay unsupported.
+#define DISPATCH_FT2C(VA, X, NAME, ...)                                      \
+    do {                                                                     \
+        auto _ta = (VA).scalar_type();                                       \
+        auto _tv = (X).scalar_type();                                        \
+        if (_ta == torch::kComplexDouble && _tv == torch::kComplexDouble) {  \
+            using scalar_a = cplx<double>;                                   \
+            using scalar_v = cplx<double>;                                   \
+            __VA_ARGS__();                                                   \
+        } else if (_ta == torch::kComplexFloat &&                            \
+                   _tv == torch::kComplexFloat) {                            \
+            using scalar_a = cplx<float>;                                    \
+            using scalar_v = cplx<float>;                                    \
+            __VA_ARGS__();                                                   \
+        } else if (_ta == torch::kComplexFloat &&                            \
+                   _tv == torch::kComplexDouble) {                           \
+            using scalar_a = cplx<float>;                                    \
+            using scalar_v = cplx<double>;                                   \
+            __VA_ARGS__();                                                   \
+        } else {                                                             \
+            DISPATCH_FT2(VA, X, NAME, __VA_ARGS__);                          \
+        }                                                                    \
+    } while (0)
+
 // f(c, s, e) for every non-empty color c = slots [s, e) of rows_sorted, in
 // ascending or descending color order
 template <typename F>
@@ -65,28 +147,36 @@ void for_each_color(const std::vector<int64_t>& bounds, bool ascending, F f) {
 }
 
 // ---------------------------------------------------------------- SpMV
+template <typename TA, typename TV>
+void csrmv_t(const Tensor& ro, const Tensor& ci, const Tensor& va,
+             int64_t block_dim, const Tensor& x, const Tensor& y,
+             const c10::optional<Tensor>& bvec, cscalar alpha, cscalar beta,
+             cscalar gamma, int64_t r0, int64_t r1, double avg) {
+    const TV* bp = bvec.has_value() ? dptr<TV>(*bvec) : nullptr;
+    TV a = coef<TV>(alpha, "csrmv"), b = coef<TV>(beta, "csrmv"),
+       g = coef<TV>(gamma, "csrmv");
+    if (block_dim == 1) {
+        amgx_hip::csrmv<TA, TV>(ro.data_ptr<int>(), ci.data_ptr<int>(),
+                                dptr<TA>(va), dptr<TV>(x), dptr<TV>(y), bp, a,
+                                b, g, (int)r0, (int)r1, avg, cur_stream());
+    } else if constexpr (is_cplx<TV>::value) {
+        TORCH_CHECK(false, "csrmv: complex block matrices are unsupported");
+    } else {
+        amgx_hip::bsrmv<TA, TV>(ro.data_ptr<int>(), ci.data_ptr<int>(),
+                                dptr<TA>(va), (int)block_dim, dptr<TV>(x),
+                                dptr<TV>(y), bp, a, b, g, (int)r0, (int)r1,
+                                cur_stream());
+    }
+}
+
 void csrmv(Tensor ro, Tensor ci, Tensor va, int64_t block_dim, Tensor x,
-           Tensor y, c10::optional<Tensor> bvec, double alpha, double beta,
-           double gamma, int64_t r0, int64_t r1) {
+           Tensor y, c10::optional<Tensor> bvec, cscalar alpha, cscalar beta,
+           cscalar gamma, int64_t r0, int64_t r1) {
     check_dev(va);
     double avg = ci.numel() / std::max<double>(1.0, ro.numel() - 1);
-    DISPATCH_FT2(va, x, "csrmv", [&] {
-        const scalar_v* bp =
-            bvec.has_value() ? bvec->data_ptr<scalar_v>() : nullptr;
-        if (block_dim == 1) {
-            amgx_hip::csrmv<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_a>(), x.data_ptr<scalar_v>(),
-                y.data_ptr<scalar_v>(), bp, (scalar_v)alpha, (scalar_v)beta,
-                (scalar_v)gamma, (int)r0, (int)r1, avg, cur_stream());
-        } else {
-            amgx_hip::bsrmv<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_a>(), (int)block_dim,
-                x.data_ptr<scalar_v>(), y.data_ptr<scalar_v>(), bp,
-                (scalar_v)alpha, (scalar_v)beta, (scalar_v)gamma, (int)r0,
-                (int)r1, cur_stream());
-        }
+    DISPATCH_FT2C(va, x, "csrmv", [&] {
+        csrmv_t<scalar_a, scalar_v>(ro, ci, va, block_dim, x, y, bvec, alpha,
+                                    beta, gamma, r0, r1, avg);
     });
 }
 
@@ -106,8 +196,38 @@ void bsrmv_generic(Tensor ro, Tensor ci, Tensor va, int64_t block_dim,
 }
 
 // ---------------------------------------------------------------- BLAS
+// complex x: op 0 = sum conj(x) y in x's dtype; op 1 / 2 / 3 = sum|x|,
+// max|x|, sum|x|^2 in the matching real dtype (op 3 is complex-only: real
+// vectors take their squared norm from op 0)
+template <typename R>
+Tensor reduce_cplx(const Tensor& x, const c10::optional<Tensor>& y,
+                   int64_t op) {
+    using C = cplx<R>;
+    if (op == 0) {
+        auto out = torch::empty({1}, x.options());
+        auto ws = torch::empty({2048}, x.options());
+        TORCH_CHECK(!y.has_value() || y->numel() == x.numel(),
+                    "reduce: x and y differ in length");
+        const C* yp = y.has_value() ? dptr<C>(*y) : dptr<C>(x);
+        amgx_hip::reduce_cdot<R>(dptr<C>(x), yp, x.numel(), dptr<C>(ws),
+                                 dptr<C>(out), cur_stream());
+        return out;
+    }
+    TORCH_CHECK(op >= 1 && op <= 3, "reduce: unknown op ", op);
+    auto ropt = x.options().dtype(c10::toRealValueType(x.scalar_type()));
+    auto out = torch::empty({1}, ropt);
+    auto ws = torch::empty({2048}, ropt);
+    amgx_hip::reduce_cabs<R>(dptr<C>(x), x.numel(), (int)op, dptr<R>(ws),
+                             dptr<R>(out), cur_stream());
+    return out;
+}
+
 Tensor reduce_op(Tensor x, c10::optional<Tensor> y, int64_t op) {
     check_dev(x);
+    if (x.scalar_type() == torch::kComplexDouble)
+        return reduce_cplx<double>(x, y, op);
+    if (x.scalar_type() == torch::kComplexFloat)
+        return reduce_cplx<float>(x, y, op);
     auto out = torch::empty({1}, x.options());
     auto ws = torch::empty({2048}, x.options());
     DISPATCH_FT(x, "reduce", [&] {
@@ -120,11 +240,11 @@ Tensor reduce_op(Tensor x, c10::optional<Tensor> y, int64_t op) {
     return out;
 }
 
-void axpy(Tensor y, Tensor x, double a) {
-    DISPATCH_FT(x, "axpy", [&] {
-        amgx_hip::axpy<scalar_t>(y.data_ptr<scalar_t>(),
-                                 x.data_ptr<scalar_t>(), (scalar_t)a,
-                                 x.numel(), cur_stream());
+void axpy(Tensor y, Tensor x, cscalar a) {
+    DISPATCH_FTC(x, "axpy", [&] {
+        amgx_hip::axpy<scalar_t>(dptr<scalar_t>(y), dptr<scalar_t>(x),
+                                 coef<scalar_t>(a, "axpy"), x.numel(),
+                                 cur_stream());
     });
 }
 
@@ -199,17 +319,18 @@ void scal_drsqrt(Tensor x, Tensor s2) {
     });
 }
 
-void axpby(Tensor y, Tensor x, double a, double b) {
-    DISPATCH_FT(x, "axpby", [&] {
-        amgx_hip::axpby<scalar_t>(y.data_ptr<scalar_t>(),
-                                  x.data_ptr<scalar_t>(), (scalar_t)a,
-                                  (scalar_t)b, x.numel(), cur_stream());
+void axpby(Tensor y, Tensor x, cscalar a, cscalar b) {
+    DISPATCH_FTC(x, "axpby", [&] {
+        amgx_hip::axpby<scalar_t>(dptr<scalar_t>(y), dptr<scalar_t>(x),
+                                  coef<scalar_t>(a, "axpby"),
+                                  coef<scalar_t>(b, "axpby"), x.numel(),
+                                  cur_stream());
     });
 }
 
-void scal(Tensor x, double a) {
-    DISPATCH_FT(x, "scal", [&] {
-        amgx_hip::scal<scalar_t>(x.data_ptr<scalar_t>(), (scalar_t)a,
+void scal(Tensor x, cscalar a) {
+    DISPATCH_FTC(x, "scal", [&] {
+        amgx_hip::scal<scalar_t>(dptr<scalar_t>(x), coef<scalar_t>(a, "scal"),
                                  x.numel(), cur_stream());
     });
 }
@@ -226,13 +347,12 @@ Tensor extract_diag(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
                     int64_t b) {
     auto out = b == 1 ? torch::empty({n}, va.options())
                       : torch::empty({n, b, b}, va.options());
-    DISPATCH_FT(va, "extract_diag", [&] {
+    DISPATCH_FTC(va, "extract_diag", [&] {
         amgx_hip::extract_diag<scalar_t>(ro.data_ptr<int>(),
                                          ci.data_ptr<int>(),
-                                         va.data_ptr<scalar_t>(),
+                                         dptr<scalar_t>(va),
                                          didx.data_ptr<int>(), (int)n, (int)b,
-                                         out.data_ptr<scalar_t>(),
-                                         cur_stream());
+                                         dptr<scalar_t>(out), cur_stream());
     });
     return out;
 }
@@ -249,6 +369,19 @@ Tensor jacobi_dinv(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
                    int64_t b, bool l1) {
     auto out = b == 1 ? torch::empty({n}, va.options())
                       : torch::empty({n, b, b}, va.options());
+    if (va.is_complex()) {   // plain scalar only
+        TORCH_CHECK(b == 1 && !l1, "jacobi_dinv: complex matrices support "
+                    "neither blocks nor the l1 variant");
+        if (va.scalar_type() == torch::kComplexDouble)
+            amgx_hip::jacobi_dinv_plain<cplx<double>>(
+                dptr<cplx<double>>(va), didx.data_ptr<int>(), (int)n,
+                dptr<cplx<double>>(out), cur_stream());
+        else
+            amgx_hip::jacobi_dinv_plain<cplx<float>>(
+                dptr<cplx<float>>(va), didx.data_ptr<int>(), (int)n,
+                dptr<cplx<float>>(out), cur_stream());
+        return out;
+    }
     DISPATCH_FT(va, "jacobi_dinv", [&] {
         amgx_hip::jacobi_dinv<scalar_t>(ro.data_ptr<int>(), ci.data_ptr<int>(),
                                         va.data_ptr<scalar_t>(),
@@ -263,12 +396,14 @@ void jacobi_smooth(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                    Tensor bvec, Tensor xi, Tensor xo, double omega) {
     int n = (int)(ro.numel() - 1);
     double avg = ci.numel() / std::max<double>(1.0, n);
-    DISPATCH_FT2(va, xi, "jacobi_smooth", [&] {
+    TORCH_CHECK(b == 1 || !va.is_complex(),
+                "jacobi_smooth: complex block matrices are unsupported");
+    DISPATCH_FT2C(va, xi, "jacobi_smooth", [&] {
         amgx_hip::jacobi_smooth<scalar_a, scalar_v>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_a>(),
-            dinv.data_ptr<scalar_a>(), bvec.data_ptr<scalar_v>(),
-            xi.data_ptr<scalar_v>(), xo.data_ptr<scalar_v>(), (scalar_v)omega,
-            n, (int)b, avg, cur_stream());
+            ro.data_ptr<int>(), ci.data_ptr<int>(), dptr<scalar_a>(va),
+            dptr<scalar_a>(dinv), dptr<scalar_v>(bvec), dptr<scalar_v>(xi),
+            dptr<scalar_v>(xo), scalar_v(omega), n, (int)b, avg,
+            cur_stream());
     });
 }
 

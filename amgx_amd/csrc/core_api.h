@@ -7,11 +7,15 @@
 
 #include <cstdint>
 
+#include "cplx.h"
+
 namespace amgx_hip {
 
 // ---- SpMV family (csrmv.hip) ------------------------------------------------
 // Mixed precision: TA = matrix-value type, TV = vector type (reference dDFI);
-// instantiated for (d,d), (f,f), (f,d).
+// instantiated for (d,d), (f,f), (f,d) and, csrmv and jacobi_smooth only,
+// for the complex pairs (cplx<double>, cplx<double>), (cplx<float>,
+// cplx<float>), (cplx<float>, cplx<double>) — reference dZZI / dCCI / dZCI.
 // y[i] = alpha * (A x)[i] + beta * y[i] + gamma * b[i]  over rows [r0, r1)
 template <typename TA, typename TV>
 void csrmv(const int* ro, const int* ci, const TA* va, const TV* x, TV* y,
@@ -117,6 +121,18 @@ template <typename T>
 void reduce(const T* x, const T* y, long long n, int op, T* ws, T* out,
             hipStream_t s);
 
+// complex reductions, same fixed two-stage tree. reduce_cdot: sum conj(x) y.
+// reduce_cabs: op 1 = sum|x|, 2 = max|x|, 3 = sum|x|^2, all accumulated and
+// returned in the real type R; ws as above.
+template <typename R>
+void reduce_cdot(const cplx<R>* x, const cplx<R>* y, long long n, cplx<R>* ws,
+                 cplx<R>* out, hipStream_t s);
+template <typename R>
+void reduce_cabs(const cplx<R>* x, long long n, int op, R* ws, R* out,
+                 hipStream_t s);
+
+// axpy / axpby / scal / extract_diag are also instantiated for cplx<float>
+// and cplx<double>; axpy_dalpha and scal_drsqrt are real-only.
 template <typename T>
 void axpy(T* y, const T* x, T a, long long n, hipStream_t s);
 template <typename T>
@@ -141,6 +157,10 @@ void trans_index(const int* ro, const int* ci, int n, int nnz, int* out,
 template <typename T>
 void jacobi_dinv(const int* ro, const int* ci, const T* va, const int* didx,
                  int n, int b, bool l1, T* dinv, hipStream_t s);
+// scalar 1/d without the l1 term (complex modes; |d| == 0 gives 1)
+template <typename T>
+void jacobi_dinv_plain(const T* va, const int* didx, int n, T* dinv,
+                       hipStream_t s);
 // xo = xi + omega * dinv * (b - A xi)   (block-aware; b=1 scalar fast path)
 template <typename TA, typename TV>
 void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,

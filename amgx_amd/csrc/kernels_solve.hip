@@ -9,6 +9,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "common.h"
 #include "core_api.h"
@@ -171,11 +172,75 @@ template <typename T, int OP>
 __global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage2(const T* __restrict__ part, int nparts, T* out) {
     T acc = T(0);
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        if (OP == 2) acc = part[i] > acc ? part[i] : acc;
+        if constexpr (OP == 2) acc = part[i] > acc ? part[i] : acc;
         else acc += part[i];
     }
-    T r = (OP == 2) ? block_reduce_max(acc) : block_reduce_sum(acc);
+    T r;
+    if constexpr (OP == 2) r = block_reduce_max(acc);
+    else r = block_reduce_sum(acc);
     if (threadIdx.x == 0) *out = r;
+}
+
+// Complex stage 1. OP 0: sum conj(x_i) y_i, complex partials. OP 1 sum|x_i|,
+// OP 2 max|x_i|, OP 3 sum|x_i|^2: real accumulators and real partials, so a
+// squared 2-norm is exactly real and non-negative. Stage 2 is the fold
+// above on the partial type.
+template <typename R, int OP>
+__global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage1_cplx(
+    const cplx<R>* __restrict__ x, const cplx<R>* __restrict__ y, long long n,
+    std::conditional_t<OP == 0, cplx<R>, R>* __restrict__ part) {
+    using A = std::conditional_t<OP == 0, cplx<R>, R>;
+    long long stride = (long long)gridDim.x * blockDim.x;
+    A acc = A(0);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        if constexpr (OP == 0) acc += conj_mul(x[i], y[i]);
+        else if constexpr (OP == 1) acc += abs(x[i]);
+        else if constexpr (OP == 2) {
+            R a = abs(x[i]);
+            acc = a > acc ? a : acc;
+        } else acc += abs2(x[i]);
+    }
+    A r;
+    if constexpr (OP == 2) r = block_reduce_max(acc);
+    else r = block_reduce_sum(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+template <typename R>
+void reduce_cdot(const cplx<R>* x, const cplx<R>* y, long long n, cplx<R>* ws,
+                 cplx<R>* out, hipStream_t s) {
+    int g = grid_1d(n, AMGX_BLOCK, NPART);
+    hipLaunchKernelGGL((reduce_stage1_cplx<R, 0>), dim3(g), dim3(AMGX_BLOCK),
+                       0, s, x, y, n, ws);
+    hipLaunchKernelGGL((reduce_stage2<cplx<R>, 0>), dim3(1), dim3(AMGX_BLOCK),
+                       0, s, ws, g, out);
+}
+
+template <typename R>
+void reduce_cabs(const cplx<R>* x, long long n, int op, R* ws, R* out,
+                 hipStream_t s) {
+    int g = grid_1d(n, AMGX_BLOCK, NPART);
+    const cplx<R>* none = nullptr;
+    switch (op) {
+        case 1:
+            hipLaunchKernelGGL((reduce_stage1_cplx<R, 1>), dim3(g),
+                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
+            hipLaunchKernelGGL((reduce_stage2<R, 1>), dim3(1),
+                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
+            break;
+        case 2:
+            hipLaunchKernelGGL((reduce_stage1_cplx<R, 2>), dim3(g),
+                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
+            hipLaunchKernelGGL((reduce_stage2<R, 2>), dim3(1),
+                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
+            break;
+        default:
+            hipLaunchKernelGGL((reduce_stage1_cplx<R, 3>), dim3(g),
+                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
+            hipLaunchKernelGGL((reduce_stage2<R, 1>), dim3(1),
+                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
+    }
 }
 
 template <typename T>
@@ -425,6 +490,27 @@ void jacobi_dinv(const int* ro, const int* ci, const T* va, const int* didx,
                            dim3(AMGX_BLOCK), 0, s, ro, ci, va, didx, n, b, l1,
                            dinv);
     }
+}
+
+// plain scalar 1/d for value types without an ordering (complex modes): the
+// l1 variant above needs fabs and a sign. |d| == 0 gives 1, as on the host.
+template <typename T>
+__global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_plain_kernel(const T* __restrict__ va,
+                                         const int* __restrict__ didx, int n,
+                                         T* __restrict__ dinv) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int dk = didx[i];
+    T d = dk >= 0 ? va[dk] : T(0);
+    if (d == T(0)) d = T(1);
+    dinv[i] = T(1) / d;
+}
+
+template <typename T>
+void jacobi_dinv_plain(const T* va, const int* didx, int n, T* dinv,
+                       hipStream_t s) {
+    hipLaunchKernelGGL((jacobi_dinv_plain_kernel<T>), dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, va, didx, n, dinv);
 }
 
 // fused damped Jacobi sweep: xo = xi + omega*dinv*(b - A xi), single pass.
@@ -1144,5 +1230,38 @@ INSTANTIATE(float)
 INSTANTIATE_MIXED(double, double)
 INSTANTIATE_MIXED(float, float)
 INSTANTIATE_MIXED(float, double)
+
+// complex modes dZZI / dCCI / dZCI: the Krylov + Jacobi subset, scalar CSR.
+// The template bodies are the real ones; sweeps, setup and transfer kernels
+// get no complex instantiation.
+#define INSTANTIATE_CPLX(R)                                                     \
+    template void reduce_cdot<R>(const cplx<R>*, const cplx<R>*, long long,     \
+                                 cplx<R>*, cplx<R>*, hipStream_t);              \
+    template void reduce_cabs<R>(const cplx<R>*, long long, int, R*, R*,        \
+                                 hipStream_t);                                  \
+    template void axpy<cplx<R>>(cplx<R>*, const cplx<R>*, cplx<R>, long long,   \
+                                hipStream_t);                                   \
+    template void axpby<cplx<R>>(cplx<R>*, const cplx<R>*, cplx<R>, cplx<R>,    \
+                                 long long, hipStream_t);                       \
+    template void scal<cplx<R>>(cplx<R>*, cplx<R>, long long, hipStream_t);     \
+    template void extract_diag<cplx<R>>(const int*, const int*,                 \
+                                        const cplx<R>*, const int*, int, int,   \
+                                        cplx<R>*, hipStream_t);                 \
+    template void jacobi_dinv_plain<cplx<R>>(const cplx<R>*, const int*, int,   \
+                                             cplx<R>*, hipStream_t);
+
+#define INSTANTIATE_CPLX_MIXED(TA, TV)                                          \
+    template void csrmv<TA, TV>(const int*, const int*, const TA*, const TV*,   \
+                                TV*, const TV*, TV, TV, TV, int, int, double,   \
+                                hipStream_t);                                   \
+    template void jacobi_smooth<TA, TV>(const int*, const int*, const TA*,      \
+                                        const TA*, const TV*, const TV*, TV*,   \
+                                        TV, int, int, double, hipStream_t);
+
+INSTANTIATE_CPLX(double)
+INSTANTIATE_CPLX(float)
+INSTANTIATE_CPLX_MIXED(cplx<double>, cplx<double>)
+INSTANTIATE_CPLX_MIXED(cplx<float>, cplx<float>)
+INSTANTIATE_CPLX_MIXED(cplx<float>, cplx<double>)
 
 }  // namespace amgx_hip

@@ -89,11 +89,22 @@ def residual(A, x, b, r=None, row_begin=0, row_end=-1):
 
 
 # ---------------------------------------------------------------------- BLAS-1
+def _coef(v, alpha):
+    """Coefficient for a kernel on ``v``: complex vectors (dZZI / dCCI / dZCI
+    modes) take it as complex, real ones as float exactly as before."""
+    return complex(alpha) if v.is_complex() else float(alpha)
+
+
 def dot(x, y):
-    return float(_core.reduce_op(x.reshape(-1), y.reshape(-1), 0).item())
+    r = _core.reduce_op(x.reshape(-1), y.reshape(-1), 0).item()
+    # complex: conj(x) . y, the convention of ops/cpu.py (torch.vdot)
+    return complex(r) if x.is_complex() else float(r)
 
 
 def nrm2(x):
+    if x.is_complex():
+        # real accumulation of re^2 + im^2 (op 3), not Re(vdot(x, x))
+        return math.sqrt(float(_core.reduce_op(x.reshape(-1), None, 3).item()))
     return math.sqrt(max(float(_core.reduce_op(x.reshape(-1), x.reshape(-1),
                                                0).item()), 0.0))
 
@@ -107,7 +118,9 @@ def nrmmax(x):
 
 
 def dot_async(x, y):
-    """Device-scalar dot (no host sync) for fused/graph paths."""
+    """Device-scalar dot (no host sync) for fused/graph paths; real only."""
+    if x.is_complex():
+        raise TypeError("dot_async is real-only (complex modes use dot)")
     return _core.reduce_op(x.reshape(-1), y.reshape(-1), 0)
 
 
@@ -126,22 +139,27 @@ def scal_drsqrt(x, s2):
 
 
 def axpy(y, x, alpha):
-    _core.axpy(y.reshape(-1), x.reshape(-1), float(alpha))
+    _core.axpy(y.reshape(-1), x.reshape(-1), _coef(x, alpha))
     return y
 
 
 def axpby(y, x, alpha, beta):
-    _core.axpby(y.reshape(-1), x.reshape(-1), float(alpha), float(beta))
+    _core.axpby(y.reshape(-1), x.reshape(-1), _coef(x, alpha),
+                _coef(x, beta))
     return y
 
 
 def scal(x, alpha):
-    _core.scal(x.reshape(-1), float(alpha))
+    _core.scal(x.reshape(-1), _coef(x, alpha))
     return x
 
 
 # ---------------------------------------------------------------------- smoothers
 def jacobi_dinv(A, l1: bool = False):
+    if l1 and A.values.is_complex():
+        raise NotImplementedError(
+            "JACOBI_L1 is not available in the complex modes (dZZI / dCCI / "
+            "dZCI): the device l1 diagonal is real-only")
     return _core.jacobi_dinv(A.row_offsets, A.col_indices, A.values, _didx(A),
                              A.n_rows, A.block_dim, bool(l1))
 

@@ -67,6 +67,16 @@ def main():
     rec("csrmv_mixed_f32A", bench(lambda: ops.spmv(A32, x, y),
                                   args.iters, sync),
         nnz * 8 + (n + 1) * 4 + n * 16)   # fp32 vals: half the value bytes
+    # complex128 (dZZI) on the same pattern, same bytes model: 16 B value +
+    # 4 B column per nnz (12 B in the real row), x and y counted once
+    Az = CSRMatrix(A.row_offsets, A.col_indices,
+                   torch.complex(A.values, 0.25 * A.values), n_cols=A.n_cols)
+    xz = torch.complex(x, torch.rand_like(x))
+    yz = torch.zeros_like(xz)
+    rec("csrmv_complex128", bench(lambda: ops.spmv(Az, xz, yz),
+                                  args.iters, sync),
+        nnz * 20 + (n + 1) * 4 + n * 16 * 2)
+    del Az, xz, yz
     r = torch.zeros_like(x)
     rec("residual_fused", bench(lambda: ops.residual(A, x, b, r),
                                 args.iters, sync), spmv_bytes + n * 8)
