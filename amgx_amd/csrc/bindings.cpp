@@ -9,8 +9,8 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <pybind11/complex.h>
 
+#include <array>
 #include <complex>
-#include <type_traits>
 #include <vector>
 
 #include "core_api.h"
@@ -23,47 +23,15 @@ hipStream_t cur_stream() {
     return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
 }
 
-#define DISPATCH_FT(TENSOR, NAME, ...)                                  \
-    AT_DISPATCH_FLOATING_TYPES(TENSOR.scalar_type(), NAME, __VA_ARGS__)
-
-// two-type dispatch for matrix-value x vector mixed ops (reference value
-// modes dDDI / dFFI / dDFI): VA drives scalar_a, X drives scalar_v
-#define DISPATCH_FT2(VA, X, NAME, ...)                                       \
-    do {                                                                     \
-        auto _ta = (VA).scalar_type();                                       \
-        auto _tv = (X).scalar_type();                                        \
-        if (_ta == torch::kFloat64 && _tv == torch::kFloat64) {              \
-            using scalar_a = double;                                         \
-            using scalar_v = double;                                         \
-            __VA_ARGS__();                                                   \
-        } else if (_ta == torch::kFloat32 && _tv == torch::kFloat32) {       \
-            using scalar_a = float;                                          \
-            using scalar_v = float;                                          \
-            __VA_ARGS__();                                                   \
-        } else if (_ta == torch::kFloat32 && _tv == torch::kFloat64) {       \
-            using scalar_a = float;                                          \
-            using scalar_v = double;                                         \
-            __VA_ARGS__();                                                   \
-        } else {                                                             \
-            TORCH_CHECK(false, NAME,                                         \
-                        ": unsupported (matrix, vector) dtype pair ", _ta,   \
-                        " x ", _tv);                                         \
-        }                                                                    \
-    } while (0)
-
 inline void check_dev(const Tensor& t) {
     TORCH_CHECK(t.is_cuda(), "amgx_amd._core requires device tensors");
 }
 
-// ---- complex modes (dZZI / dCCI / dZCI) ------------------------------------
-// Only the entries of the Krylov + Jacobi path dispatch through the *C
-// macros below; every other entry keeps the real-only dispatch and raises on
-// complex tensors.
+// ---- element types ---------------------------------------------------------
 using amgx_hip::cplx;
+using amgx_hip::is_cplx;
 using cscalar = std::complex<double>;   // coefficient as it arrives from Python
 
-template <typename T> struct is_cplx : std::false_type {};
-template <typename R> struct is_cplx<cplx<R>> : std::true_type {};
 template <typename T> struct tensor_elem { using type = T; };
 template <typename R> struct tensor_elem<cplx<R>> { using type = c10::complex<R>; };
 static_assert(sizeof(cplx<float>) == sizeof(c10::complex<float>) &&
@@ -76,6 +44,8 @@ template <typename T>
 T* dptr(const Tensor& t) {
     return reinterpret_cast<T*>(t.data_ptr<typename tensor_elem<T>::type>());
 }
+// the int32 index arrays: row offsets, columns, permutations, colors
+inline int* iptr(const Tensor& t) { return dptr<int>(t); }
 
 // coefficient in the kernel's scalar type; a real kernel takes no imaginary part
 template <typename T>
@@ -89,50 +59,42 @@ T coef(cscalar a, const char* name) {
     }
 }
 
-#define DISPATCH_FTC(TENSOR, NAME, ...)                                      \
-    do {                                                                     \
-        auto _t = (TENSOR).scalar_type();                                    \
-        if (_t == torch::kFloat64) {                                         \
-            using scalar_t = double;                                         \
-            __VA_ARGS__();                                                   \
-        } else if (_t == torch::kFloat32) {                                  \
-            using scalar_t = float;                                          \
-            __VA_ARGS__();                                                   \
-        } else if (_t == torch::kComplexDouble) {                            \
-            using scalar_t = cplx<double>;                                   \
-            __VA_ARGS__();                                                   \
-        } else if (_t == torch::kComplexFloat) {                             \
-            using scalar_t = cplx<float>;                                    \
-            __VA_ARGS__();                                                   \
-        } else {                                                             \
-            TORCH_CHECK(false, NAME, ": unsupported dtype ", _t);            \
-        }                                                                    \
-    } while (0)
+// ---- dispatch --------------------------------------------------------------
+// DISPATCH(LIST, NAME, (tensors), body) calls body, a lambda without
+// arguments, for the entry of LIST whose element types are the dtypes of the
+// tensors. LIST is a type or pair list of core_api.h, the same one the
+// launchers in body are instantiated over. With a type list and (t), body
+// sees the entry as scalar_t; with a pair list and (va, x), as scalar_a
+// (matrix values) and scalar_v (vectors). Any other dtype or pair raises, so
+// an entry over a real list rejects complex tensors.
+template <typename... Tn>
+std::array<c10::ScalarType, sizeof...(Tn)> dtypes(const Tn&... t) {
+    return {t.scalar_type()...};
+}
+template <typename... Ts>
+constexpr std::array<c10::ScalarType, sizeof...(Ts)> dtypes_of() {
+    return {c10::CppTypeToScalarType<
+        typename tensor_elem<Ts>::type>::value...};
+}
+template <typename TA, typename TV = TA>
+struct list_entry { using a = TA; using v = TV; };
 
-// DISPATCH_FT2 plus the complex pairs (Z,Z), (C,C), (C,Z). Complex x real,
-// real x complex and Z x C stay unsupported.
-#define DISPATCH_FT2C(VA, X, NAME, ...)                                      \
-    do {                                                                     \
-        auto _ta = (VA).scalar_type();                                       \
-        auto _tv = (X).scalar_type();                                        \
-        if (_ta == torch::kComplexDouble && _tv == torch::kComplexDouble) {  \
-            using scalar_a = cplx<double>;                                   \
-            using scalar_v = cplx<double>;                                   \
-            __VA_ARGS__();                                                   \
-        } else if (_ta == torch::kComplexFloat &&                            \
-                   _tv == torch::kComplexFloat) {                            \
-            using scalar_a = cplx<float>;                                    \
-            using scalar_v = cplx<float>;                                    \
-            __VA_ARGS__();                                                   \
-        } else if (_ta == torch::kComplexFloat &&                            \
-                   _tv == torch::kComplexDouble) {                           \
-            using scalar_a = cplx<float>;                                    \
-            using scalar_v = cplx<double>;                                   \
-            __VA_ARGS__();                                                   \
-        } else {                                                             \
-            DISPATCH_FT2(VA, X, NAME, __VA_ARGS__);                          \
-        }                                                                    \
-    } while (0)
+#define DISPATCH_CASE(...)                                                   \
+    if (_key == dtypes_of<__VA_ARGS__>())                                    \
+        return _body(list_entry<__VA_ARGS__>{});
+#define DISPATCH(LIST, NAME, TENSORS, ...)                                   \
+    [&] {                                                                    \
+        const auto _key = dtypes TENSORS;                                    \
+        auto _body = [&](auto _e) {                                          \
+            using scalar_t [[maybe_unused]] = typename decltype(_e)::a;      \
+            using scalar_a [[maybe_unused]] = typename decltype(_e)::a;      \
+            using scalar_v [[maybe_unused]] = typename decltype(_e)::v;      \
+            (__VA_ARGS__)();                                                 \
+        };                                                                   \
+        LIST(DISPATCH_CASE)                                                  \
+        TORCH_CHECK(false, NAME, ": unsupported dtype ",                     \
+                    c10::Join(" x ", _key));                                 \
+    }()
 
 // f(c, s, e) for every non-empty color c = slots [s, e) of rows_sorted, in
 // ascending or descending color order
@@ -156,16 +118,15 @@ void csrmv_t(const Tensor& ro, const Tensor& ci, const Tensor& va,
     TV a = coef<TV>(alpha, "csrmv"), b = coef<TV>(beta, "csrmv"),
        g = coef<TV>(gamma, "csrmv");
     if (block_dim == 1) {
-        amgx_hip::csrmv<TA, TV>(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                                dptr<TA>(va), dptr<TV>(x), dptr<TV>(y), bp, a,
-                                b, g, (int)r0, (int)r1, avg, cur_stream());
+        amgx_hip::csrmv<TA, TV>(iptr(ro), iptr(ci), dptr<TA>(va), dptr<TV>(x),
+                                dptr<TV>(y), bp, a, b, g, (int)r0, (int)r1,
+                                avg, cur_stream());
     } else if constexpr (is_cplx<TV>::value) {
         TORCH_CHECK(false, "csrmv: complex block matrices are unsupported");
     } else {
-        amgx_hip::bsrmv<TA, TV>(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                                dptr<TA>(va), (int)block_dim, dptr<TV>(x),
-                                dptr<TV>(y), bp, a, b, g, (int)r0, (int)r1,
-                                cur_stream());
+        amgx_hip::bsrmv<TA, TV>(iptr(ro), iptr(ci), dptr<TA>(va),
+                                (int)block_dim, dptr<TV>(x), dptr<TV>(y), bp,
+                                a, b, g, (int)r0, (int)r1, cur_stream());
     }
 }
 
@@ -174,7 +135,7 @@ void csrmv(Tensor ro, Tensor ci, Tensor va, int64_t block_dim, Tensor x,
            cscalar gamma, int64_t r0, int64_t r1) {
     check_dev(va);
     double avg = ci.numel() / std::max<double>(1.0, ro.numel() - 1);
-    DISPATCH_FT2C(va, x, "csrmv", [&] {
+    DISPATCH(AMGX_VALUE_PAIRS, "csrmv", (va, x), [&] {
         csrmv_t<scalar_a, scalar_v>(ro, ci, va, block_dim, x, y, bvec, alpha,
                                     beta, gamma, r0, r1, avg);
     });
@@ -186,62 +147,42 @@ void bsrmv_generic(Tensor ro, Tensor ci, Tensor va, int64_t block_dim,
                    Tensor x, Tensor y, double alpha, double beta) {
     check_dev(va);
     int r1 = (int)ro.numel() - 1;
-    DISPATCH_FT2(va, x, "bsrmv_generic", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "bsrmv_generic", (va, x), [&] {
         amgx_hip::bsrmv_generic<scalar_a, scalar_v>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_a>(),
-            (int)block_dim, x.data_ptr<scalar_v>(), y.data_ptr<scalar_v>(),
-            nullptr, (scalar_v)alpha, (scalar_v)beta, (scalar_v)0, 0, r1,
-            cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_a>(va), (int)block_dim,
+            dptr<scalar_v>(x), dptr<scalar_v>(y), nullptr, (scalar_v)alpha,
+            (scalar_v)beta, (scalar_v)0, 0, r1, cur_stream());
     });
 }
 
 // ---------------------------------------------------------------- BLAS
-// complex x: op 0 = sum conj(x) y in x's dtype; op 1 / 2 / 3 = sum|x|,
-// max|x|, sum|x|^2 in the matching real dtype (op 3 is complex-only: real
-// vectors take their squared norm from op 0)
-template <typename R>
-Tensor reduce_cplx(const Tensor& x, const c10::optional<Tensor>& y,
-                   int64_t op) {
-    using C = cplx<R>;
-    if (op == 0) {
-        auto out = torch::empty({1}, x.options());
-        auto ws = torch::empty({2048}, x.options());
-        TORCH_CHECK(!y.has_value() || y->numel() == x.numel(),
-                    "reduce: x and y differ in length");
-        const C* yp = y.has_value() ? dptr<C>(*y) : dptr<C>(x);
-        amgx_hip::reduce_cdot<R>(dptr<C>(x), yp, x.numel(), dptr<C>(ws),
-                                 dptr<C>(out), cur_stream());
-        return out;
-    }
-    TORCH_CHECK(op >= 1 && op <= 3, "reduce: unknown op ", op);
-    auto ropt = x.options().dtype(c10::toRealValueType(x.scalar_type()));
-    auto out = torch::empty({1}, ropt);
-    auto ws = torch::empty({2048}, ropt);
-    amgx_hip::reduce_cabs<R>(dptr<C>(x), x.numel(), (int)op, dptr<R>(ws),
-                             dptr<R>(out), cur_stream());
-    return out;
-}
-
+// op 0 = sum conj(x) y (y defaults to x) in x's dtype; op 1 / 2 / 3 = sum|x|,
+// max|x|, sum|x|^2 in the matching real dtype. Op 3 is complex-only: real
+// vectors take their squared norm from op 0. The launcher rejects other ops.
 Tensor reduce_op(Tensor x, c10::optional<Tensor> y, int64_t op) {
     check_dev(x);
-    if (x.scalar_type() == torch::kComplexDouble)
-        return reduce_cplx<double>(x, y, op);
-    if (x.scalar_type() == torch::kComplexFloat)
-        return reduce_cplx<float>(x, y, op);
-    auto out = torch::empty({1}, x.options());
-    auto ws = torch::empty({2048}, x.options());
-    DISPATCH_FT(x, "reduce", [&] {
-        const scalar_t* yp = y.has_value() ? y->data_ptr<scalar_t>()
-                                           : x.data_ptr<scalar_t>();
-        amgx_hip::reduce<scalar_t>(x.data_ptr<scalar_t>(), yp, x.numel(),
-                                   (int)op, ws.data_ptr<scalar_t>(),
-                                   out.data_ptr<scalar_t>(), cur_stream());
+    TORCH_CHECK(!y.has_value() || y->numel() == x.numel(),
+                "reduce: x and y differ in length");
+    auto popt = op == 0 ? x.options()
+                        : x.options().dtype(
+                              c10::toRealValueType(x.scalar_type()));
+    auto out = torch::empty({1}, popt);
+    auto ws = torch::empty({2048}, popt);
+    DISPATCH(AMGX_VALUE_TYPES, "reduce", (x), [&] {
+        using real_t = typename amgx_hip::real_of<scalar_t>::type;
+        auto partial = [&](const Tensor& t) -> void* {
+            if (op == 0) return dptr<scalar_t>(t);
+            return dptr<real_t>(t);
+        };
+        amgx_hip::reduce<scalar_t>(
+            dptr<scalar_t>(x), dptr<scalar_t>(y.has_value() ? *y : x),
+            x.numel(), (int)op, partial(ws), partial(out), cur_stream());
     });
     return out;
 }
 
 void axpy(Tensor y, Tensor x, cscalar a) {
-    DISPATCH_FTC(x, "axpy", [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "axpy", (x), [&] {
         amgx_hip::axpy<scalar_t>(dptr<scalar_t>(y), dptr<scalar_t>(x),
                                  coef<scalar_t>(a, "axpy"), x.numel(),
                                  cur_stream());
@@ -263,20 +204,17 @@ std::vector<Tensor> spgemm_hash(Tensor roA, Tensor ciA, Tensor vaA,
     auto big = torch::empty({0}, roA.options());
     hipStream_t st = cur_stream();
     long long nnz = -1;
-    DISPATCH_FT(vaA, "spgemm_hash", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "spgemm_hash", (vaA), [&] {
         int* big_rows = nullptr;
         int n_big = 0;
         nnz = amgx_hip::spgemm_hash<scalar_t>(
-            roA.data_ptr<int>(), ciA.data_ptr<int>(),
-            vaA.data_ptr<scalar_t>(), m, roB.data_ptr<int>(),
-            ciB.data_ptr<int>(), vaB.data_ptr<scalar_t>(),
-            aggcol ? aggcol->data_ptr<int>() : nullptr, (int)mode,
-            (int)cap0, roC.data_ptr<int>(), ciC.data_ptr<int>(),
-            vaC.data_ptr<scalar_t>(), (long long)cap_nnz, &big_rows,
-            &n_big, st);
+            iptr(roA), iptr(ciA), dptr<scalar_t>(vaA), m, iptr(roB), iptr(ciB),
+            dptr<scalar_t>(vaB), aggcol ? iptr(*aggcol) : nullptr, (int)mode,
+            (int)cap0, iptr(roC), iptr(ciC), dptr<scalar_t>(vaC),
+            (long long)cap_nnz, &big_rows, &n_big, st);
         if (n_big > 0) {
             big = torch::empty({n_big}, roA.options());
-            TORCH_CHECK(hipMemcpyAsync(big.data_ptr<int>(), big_rows,
+            TORCH_CHECK(hipMemcpyAsync(iptr(big), big_rows,
                                        n_big * sizeof(int),
                                        hipMemcpyDeviceToDevice,
                                        st) == hipSuccess,
@@ -295,41 +233,36 @@ std::vector<Tensor> spgemm_hash(Tensor roA, Tensor ciA, Tensor vaA,
 
 Tensor mfma4_probe(Tensor a_frag, Tensor b_frag) {
     auto c = torch::empty_like(a_frag);
-    amgx_hip::mfma4_probe(a_frag.data_ptr<double>(),
-                          b_frag.data_ptr<double>(), c.data_ptr<double>(),
-                          cur_stream());
+    amgx_hip::mfma4_probe(dptr<double>(a_frag), dptr<double>(b_frag),
+                          dptr<double>(c), cur_stream());
     return c;
 }
 
 void axpy_dalpha(Tensor y, Tensor x, Tensor alpha, double scale) {
-    DISPATCH_FT(x, "axpy_dalpha", [&] {
-        amgx_hip::axpy_dalpha<scalar_t>(y.data_ptr<scalar_t>(),
-                                        x.data_ptr<scalar_t>(),
-                                        alpha.data_ptr<scalar_t>(),
-                                        (scalar_t)scale, x.numel(),
-                                        cur_stream());
+    DISPATCH(AMGX_REAL_TYPES, "axpy_dalpha", (x), [&] {
+        amgx_hip::axpy_dalpha<scalar_t>(dptr<scalar_t>(y), dptr<scalar_t>(x),
+                                        dptr<scalar_t>(alpha), (scalar_t)scale,
+                                        x.numel(), cur_stream());
     });
 }
 
 void scal_drsqrt(Tensor x, Tensor s2) {
-    DISPATCH_FT(x, "scal_drsqrt", [&] {
-        amgx_hip::scal_drsqrt<scalar_t>(x.data_ptr<scalar_t>(),
-                                        s2.data_ptr<scalar_t>(), x.numel(),
-                                        cur_stream());
+    DISPATCH(AMGX_REAL_TYPES, "scal_drsqrt", (x), [&] {
+        amgx_hip::scal_drsqrt<scalar_t>(dptr<scalar_t>(x), dptr<scalar_t>(s2),
+                                        x.numel(), cur_stream());
     });
 }
 
 void axpby(Tensor y, Tensor x, cscalar a, cscalar b) {
-    DISPATCH_FTC(x, "axpby", [&] {
-        amgx_hip::axpby<scalar_t>(dptr<scalar_t>(y), dptr<scalar_t>(x),
-                                  coef<scalar_t>(a, "axpby"),
-                                  coef<scalar_t>(b, "axpby"), x.numel(),
-                                  cur_stream());
+    DISPATCH(AMGX_VALUE_TYPES, "axpby", (x), [&] {
+        amgx_hip::axpby<scalar_t>(
+            dptr<scalar_t>(y), dptr<scalar_t>(x), coef<scalar_t>(a, "axpby"),
+            coef<scalar_t>(b, "axpby"), x.numel(), cur_stream());
     });
 }
 
 void scal(Tensor x, cscalar a) {
-    DISPATCH_FTC(x, "scal", [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "scal", (x), [&] {
         amgx_hip::scal<scalar_t>(dptr<scalar_t>(x), coef<scalar_t>(a, "scal"),
                                  x.numel(), cur_stream());
     });
@@ -338,8 +271,7 @@ void scal(Tensor x, cscalar a) {
 // ---------------------------------------------------------------- structure
 Tensor diag_index(Tensor ro, Tensor ci, int64_t n) {
     auto out = torch::empty({n}, ro.options());
-    amgx_hip::diag_index(ro.data_ptr<int>(), ci.data_ptr<int>(), (int)n,
-                         out.data_ptr<int>(), cur_stream());
+    amgx_hip::diag_index(iptr(ro), iptr(ci), (int)n, iptr(out), cur_stream());
     return out;
 }
 
@@ -347,20 +279,17 @@ Tensor extract_diag(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
                     int64_t b) {
     auto out = b == 1 ? torch::empty({n}, va.options())
                       : torch::empty({n, b, b}, va.options());
-    DISPATCH_FTC(va, "extract_diag", [&] {
-        amgx_hip::extract_diag<scalar_t>(ro.data_ptr<int>(),
-                                         ci.data_ptr<int>(),
-                                         dptr<scalar_t>(va),
-                                         didx.data_ptr<int>(), (int)n, (int)b,
-                                         dptr<scalar_t>(out), cur_stream());
+    DISPATCH(AMGX_VALUE_TYPES, "extract_diag", (va), [&] {
+        amgx_hip::extract_diag<scalar_t>(dptr<scalar_t>(va), iptr(didx),
+                                         (int)n, (int)b, dptr<scalar_t>(out),
+                                         cur_stream());
     });
     return out;
 }
 
 Tensor trans_index(Tensor ro, Tensor ci, int64_t n) {
     auto out = torch::empty({ci.numel()}, ro.options());
-    amgx_hip::trans_index(ro.data_ptr<int>(), ci.data_ptr<int>(), (int)n,
-                          (int)ci.numel(), out.data_ptr<int>(), cur_stream());
+    amgx_hip::trans_index(iptr(ro), iptr(ci), (int)n, iptr(out), cur_stream());
     return out;
 }
 
@@ -369,25 +298,13 @@ Tensor jacobi_dinv(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
                    int64_t b, bool l1) {
     auto out = b == 1 ? torch::empty({n}, va.options())
                       : torch::empty({n, b, b}, va.options());
-    if (va.is_complex()) {   // plain scalar only
-        TORCH_CHECK(b == 1 && !l1, "jacobi_dinv: complex matrices support "
-                    "neither blocks nor the l1 variant");
-        if (va.scalar_type() == torch::kComplexDouble)
-            amgx_hip::jacobi_dinv_plain<cplx<double>>(
-                dptr<cplx<double>>(va), didx.data_ptr<int>(), (int)n,
-                dptr<cplx<double>>(out), cur_stream());
-        else
-            amgx_hip::jacobi_dinv_plain<cplx<float>>(
-                dptr<cplx<float>>(va), didx.data_ptr<int>(), (int)n,
-                dptr<cplx<float>>(out), cur_stream());
-        return out;
-    }
-    DISPATCH_FT(va, "jacobi_dinv", [&] {
-        amgx_hip::jacobi_dinv<scalar_t>(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                                        va.data_ptr<scalar_t>(),
-                                        didx.data_ptr<int>(), (int)n, (int)b,
-                                        l1, out.data_ptr<scalar_t>(),
-                                        cur_stream());
+    TORCH_CHECK(!va.is_complex() || (b == 1 && !l1),
+                "jacobi_dinv: complex matrices support neither blocks nor "
+                "the l1 variant");
+    DISPATCH(AMGX_VALUE_TYPES, "jacobi_dinv", (va), [&] {
+        amgx_hip::jacobi_dinv<scalar_t>(iptr(ro), dptr<scalar_t>(va),
+                                        iptr(didx), (int)n, (int)b, l1,
+                                        dptr<scalar_t>(out), cur_stream());
     });
     return out;
 }
@@ -395,27 +312,24 @@ Tensor jacobi_dinv(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
 void jacobi_smooth(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                    Tensor bvec, Tensor xi, Tensor xo, double omega) {
     int n = (int)(ro.numel() - 1);
-    double avg = ci.numel() / std::max<double>(1.0, n);
     TORCH_CHECK(b == 1 || !va.is_complex(),
                 "jacobi_smooth: complex block matrices are unsupported");
-    DISPATCH_FT2C(va, xi, "jacobi_smooth", [&] {
+    DISPATCH(AMGX_VALUE_PAIRS, "jacobi_smooth", (va, xi), [&] {
         amgx_hip::jacobi_smooth<scalar_a, scalar_v>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), dptr<scalar_a>(va),
-            dptr<scalar_a>(dinv), dptr<scalar_v>(bvec), dptr<scalar_v>(xi),
-            dptr<scalar_v>(xo), scalar_v(omega), n, (int)b, avg,
-            cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_a>(va), dptr<scalar_a>(dinv),
+            dptr<scalar_v>(bvec), dptr<scalar_v>(xi), dptr<scalar_v>(xo),
+            scalar_v(omega), n, (int)b, cur_stream());
     });
 }
 
 void gs_smooth_rows(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                     Tensor bvec, Tensor x, Tensor rows, double omega) {
     int n = (int)(ro.numel() - 1);
-    DISPATCH_FT2(va, x, "gs_smooth_rows", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "gs_smooth_rows", (va, x), [&] {
         amgx_hip::gs_smooth_rows<scalar_a, scalar_v>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_a>(),
-            dinv.data_ptr<scalar_a>(), bvec.data_ptr<scalar_v>(),
-            x.data_ptr<scalar_v>(), rows.data_ptr<int>(), (int)rows.numel(),
-            (scalar_v)omega, n, (int)b, cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_a>(va), dptr<scalar_a>(dinv),
+            dptr<scalar_v>(bvec), dptr<scalar_v>(x), iptr(rows),
+            (int)rows.numel(), (scalar_v)omega, n, (int)b, cur_stream());
     });
 }
 
@@ -424,14 +338,12 @@ void gs_sweep(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
               Tensor bvec, Tensor x, Tensor rows_sorted,
               std::vector<int64_t> bounds, double omega, bool symmetric) {
     int n = (int)(ro.numel() - 1);
-    DISPATCH_FT2(va, x, "gs_sweep", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "gs_sweep", (va, x), [&] {
         auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_smooth_rows<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_a>(), dinv.data_ptr<scalar_a>(),
-                bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                (scalar_v)omega, n, (int)b, cur_stream());
+                iptr(ro), iptr(ci), dptr<scalar_a>(va), dptr<scalar_a>(dinv),
+                dptr<scalar_v>(bvec), dptr<scalar_v>(x), iptr(rows_sorted) + s,
+                (int)(e - s), (scalar_v)omega, n, (int)b, cur_stream());
         };
         for_each_color(bounds, true, run);
         if (symmetric) for_each_color(bounds, false, run);
@@ -446,23 +358,21 @@ void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
     int nc = (int)bounds.size() - 1;
     int64_t n = (int64_t)ro_s.numel() - 1;
     if (n <= amgx_hip::SMALL_LEVEL_ROWS) {
-        DISPATCH_FT2(va_s, x, "gs_sweep_small", [&] {
+        DISPATCH(AMGX_REAL_PAIRS, "gs_sweep_small", (va_s, x), [&] {
             amgx_hip::gs_sweep_small<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>(), ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(), dinv_s.data_ptr<scalar_a>(),
-                bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                rows_sorted.data_ptr<int>(), bounds_dev.data_ptr<int>(),
-                nc, (scalar_v)omega, symmetric, cur_stream());
+                iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
+                dptr<scalar_a>(dinv_s), dptr<scalar_v>(bvec),
+                dptr<scalar_v>(x), iptr(rows_sorted), iptr(bounds_dev), nc,
+                (scalar_v)omega, symmetric, cur_stream());
         });
         return;
     }
-    DISPATCH_FT2(va_s, x, "gs_sweep_sorted", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "gs_sweep_sorted", (va_s, x), [&] {
         auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_rows_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(), dinv_s.data_ptr<scalar_a>() + s,
-                bvec.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
+                iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(va_s),
+                dptr<scalar_a>(dinv_s) + s, dptr<scalar_v>(bvec),
+                dptr<scalar_v>(x), iptr(rows_sorted) + s, (int)(e - s),
                 (scalar_v)omega, cur_stream());
         };
         for_each_color(bounds, true, run);
@@ -477,14 +387,12 @@ Tensor dilu_setup(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor didx,
     int n = (int)(ro.numel() - 1);
     auto einv = b == 1 ? torch::zeros({n}, va.options())
                        : torch::zeros({n, b, b}, va.options());
-    DISPATCH_FT(va, "dilu_setup", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "dilu_setup", (va), [&] {
         for_each_color(bounds, true, [&](int c, int64_t s, int64_t e) {
             amgx_hip::dilu_setup_color<scalar_t>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_t>(), didx.data_ptr<int>(),
-                tidx.data_ptr<int>(), colors.data_ptr<int>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s), c,
-                einv.data_ptr<scalar_t>(), (int)b, cur_stream());
+                iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(didx), iptr(tidx),
+                iptr(colors), iptr(rows_sorted) + s, (int)(e - s), c,
+                dptr<scalar_t>(einv), (int)b, cur_stream());
         });
     });
     return einv;
@@ -508,42 +416,37 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
     // small levels: ONE fused single-WG launch for the whole apply
     // (zeroing + all colors both sweeps + relaxed axpy)
     if (b == 1 && n <= amgx_hip::SMALL_LEVEL_ROWS) {
-        DISPATCH_FT2(va_s, x, "dilu_small", [&] {
+        DISPATCH(AMGX_REAL_PAIRS, "dilu_small", (va_s, x), [&] {
             amgx_hip::dilu_small<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>(), ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(), einv_s.data_ptr<scalar_a>(),
-                rows_sorted.data_ptr<int>(), bounds_dev.data_ptr<int>(), nc,
-                rhs.data_ptr<scalar_v>(), w.data_ptr<scalar_v>(),
-                z.data_ptr<scalar_v>(), x.data_ptr<scalar_v>(),
-                (scalar_v)relax, (long long)w.numel(), fused, cur_stream());
+                iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
+                dptr<scalar_a>(einv_s), iptr(rows_sorted), iptr(bounds_dev),
+                nc, dptr<scalar_v>(rhs), dptr<scalar_v>(w), dptr<scalar_v>(z),
+                dptr<scalar_v>(x), (scalar_v)relax, (long long)w.numel(),
+                fused, cur_stream());
         });
         return;
     }
     w.zero_();
     z.zero_();
-    DISPATCH_FT2(va_s, x, "dilu_sorted", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "dilu_sorted", (va_s, x), [&] {
         hipStream_t st = cur_stream();
-        const scalar_v* xres = fused ? x.data_ptr<scalar_v>() : nullptr;
+        const scalar_v* xres = fused ? dptr<scalar_v>(x) : nullptr;
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_fwd_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(),
-                einv_s.data_ptr<scalar_a>() + s * bb,
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                rhs.data_ptr<scalar_v>(), xres, w.data_ptr<scalar_v>(),
+                iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(va_s),
+                dptr<scalar_a>(einv_s) + s * bb, iptr(rows_sorted) + s,
+                (int)(e - s), dptr<scalar_v>(rhs), xres, dptr<scalar_v>(w),
                 (int)b, st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_bwd_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                va_s.data_ptr<scalar_a>(),
-                einv_s.data_ptr<scalar_a>() + s * bb,
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                w.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), (int)b, st);
+                iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(va_s),
+                dptr<scalar_a>(einv_s) + s * bb, iptr(rows_sorted) + s,
+                (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(z), (int)b,
+                st);
         });
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
+        amgx_hip::axpy<scalar_v>(dptr<scalar_v>(x), dptr<scalar_v>(z),
+                                 (scalar_v)relax, x.numel(), st);
     });
 }
 
@@ -563,11 +466,9 @@ std::tuple<Tensor, int64_t> color_minmax(Tensor ro, Tensor ci, int64_t n,
     for (; rounds < max_rounds; ++rounds) {
         counter.zero_();
         int mode = rounds < mode1_rounds ? 1 : 0;
-        amgx_hip::color_minmax_round(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                                     (int)n, colors.data_ptr<int>(),
-                                     colors_next.data_ptr<int>(), rounds,
-                                     (int)(seed + rounds * 7919), mode,
-                                     counter.data_ptr<int>(), st);
+        amgx_hip::color_minmax_round(
+            iptr(ro), iptr(ci), (int)n, iptr(colors), iptr(colors_next),
+            rounds, (int)(seed + rounds * 7919), mode, iptr(counter), st);
         std::swap(colors, colors_next);
         int left = counter.cpu().item<int>();
         if (left == 0) break;
@@ -586,24 +487,21 @@ Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
     auto prop = torch::empty({n}, ro.options().dtype(torch::kInt32));
     auto changed = torch::zeros({1}, ro.options().dtype(torch::kInt32));
     hipStream_t st = cur_stream();
-    DISPATCH_FT(va, "size2_match", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "size2_match", (va), [&] {
         for (int it = 0; it < max_iters; ++it) {
             amgx_hip::agg_propose<scalar_t>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(),
-                va.data_ptr<scalar_t>(), tidx.data_ptr<int>(),
-                diag.data_ptr<scalar_t>(), (int)n, agg.data_ptr<int>(),
-                prop.data_ptr<int>(), (int)seed, st);
+                iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
+                dptr<scalar_t>(diag), (int)n, iptr(agg), iptr(prop), (int)seed,
+                st);
             changed.zero_();
-            amgx_hip::agg_match(prop.data_ptr<int>(), (int)n,
-                                agg.data_ptr<int>(), changed.data_ptr<int>(),
+            amgx_hip::agg_match(iptr(prop), (int)n, iptr(agg), iptr(changed),
                                 st);
             if (changed.cpu().item<int>() == 0) break;
         }
         auto agg_out = torch::empty_like(agg);
         amgx_hip::agg_merge_singletons<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            tidx.data_ptr<int>(), diag.data_ptr<scalar_t>(), (int)n,
-            agg.data_ptr<int>(), agg_out.data_ptr<int>(), st);
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
+            dptr<scalar_t>(diag), (int)n, iptr(agg), iptr(agg_out), st);
         agg = agg_out;
     });
     return agg;   // root fine-node ids; Python renumbers with torch.unique
@@ -612,52 +510,44 @@ Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
 // ---------------------------------------------------------------- transfers
 void restrict_agg(Tensor r, Tensor agg, int64_t b, Tensor rc) {
     rc.zero_();
-    DISPATCH_FT(r, "restrict_agg", [&] {
-        amgx_hip::restrict_agg<scalar_t>(r.data_ptr<scalar_t>(),
-                                         agg.data_ptr<int>(),
+    DISPATCH(AMGX_REAL_TYPES, "restrict_agg", (r), [&] {
+        amgx_hip::restrict_agg<scalar_t>(dptr<scalar_t>(r), iptr(agg),
                                          (int)agg.numel(), (int)b,
-                                         rc.data_ptr<scalar_t>(),
-                                         cur_stream());
+                                         dptr<scalar_t>(rc), cur_stream());
     });
 }
 
 void restrict_csr(Tensor r, Tensor off, Tensor fids, int64_t b, Tensor rc) {
-    DISPATCH_FT(r, "restrict_csr", [&] {
-        amgx_hip::restrict_csr<scalar_t>(off.data_ptr<int>(),
-                                         fids.data_ptr<int>(),
-                                         r.data_ptr<scalar_t>(),
-                                         (int)(off.numel() - 1), (int)b,
-                                         rc.data_ptr<scalar_t>(),
-                                         cur_stream());
+    DISPATCH(AMGX_REAL_TYPES, "restrict_csr", (r), [&] {
+        amgx_hip::restrict_csr<scalar_t>(
+            iptr(off), iptr(fids), dptr<scalar_t>(r), (int)(off.numel() - 1),
+            (int)b, dptr<scalar_t>(rc), cur_stream());
     });
 }
 
 void prolongate_agg(Tensor x, Tensor xc, Tensor agg, int64_t b) {
-    DISPATCH_FT(x, "prolongate_agg", [&] {
-        amgx_hip::prolongate_agg<scalar_t>(x.data_ptr<scalar_t>(),
-                                           xc.data_ptr<scalar_t>(),
-                                           agg.data_ptr<int>(),
-                                           (int)agg.numel(), (int)b,
-                                           cur_stream());
+    DISPATCH(AMGX_REAL_TYPES, "prolongate_agg", (x), [&] {
+        amgx_hip::prolongate_agg<scalar_t>(
+            dptr<scalar_t>(x), dptr<scalar_t>(xc), iptr(agg), (int)agg.numel(),
+            (int)b, cur_stream());
     });
 }
 
 // ---------------------------------------------------------------- dense
 void dense_gemv(Tensor Ainv, Tensor b, Tensor x) {
-    DISPATCH_FT2(Ainv, b, "dense_gemv", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "dense_gemv", (Ainv, b), [&] {
         amgx_hip::dense_gemv<scalar_a, scalar_v>(
-            Ainv.data_ptr<scalar_a>(), b.data_ptr<scalar_v>(),
-            x.data_ptr<scalar_v>(), (int)b.numel(), cur_stream());
+            dptr<scalar_a>(Ainv), dptr<scalar_v>(b), dptr<scalar_v>(x),
+            (int)b.numel(), cur_stream());
     });
 }
 
 // ---------------------------------------------------------------- pack
 void gather(Tensor src, Tensor idx, int64_t b, Tensor dst) {
-    DISPATCH_FT(src, "gather", [&] {
-        amgx_hip::gather<scalar_t>(src.data_ptr<scalar_t>(),
-                                   idx.data_ptr<int>(), (int)idx.numel(),
-                                   (int)b, dst.data_ptr<scalar_t>(),
-                                   cur_stream());
+    DISPATCH(AMGX_REAL_TYPES, "gather", (src), [&] {
+        amgx_hip::gather<scalar_t>(dptr<scalar_t>(src), iptr(idx),
+                                   (int)idx.numel(), (int)b,
+                                   dptr<scalar_t>(dst), cur_stream());
     });
 }
 
@@ -676,12 +566,11 @@ std::tuple<Tensor, Tensor, Tensor> galerkin_agg(Tensor ro, Tensor ci,
                     ? torch::empty({nnz}, va.options())
                     : torch::empty({nnz, block_dim, block_dim}, va.options());
     long long nnz_c = 0;
-    DISPATCH_FT(va, "galerkin_agg", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "galerkin_agg", (va), [&] {
         nnz_c = amgx_hip::galerkin_agg<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            n, nnz, agg.data_ptr<int>(), agg_col.data_ptr<int>(), (int)nc,
-            (long long)ncmod, ro_c.data_ptr<int>(), ci_c.data_ptr<int>(),
-            va_c.data_ptr<scalar_t>(), bb, cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), n, nnz, iptr(agg),
+            iptr(agg_col), (int)nc, (long long)ncmod, iptr(ro_c), iptr(ci_c),
+            dptr<scalar_t>(va_c), bb, cur_stream());
     });
     return {ro_c, ci_c.narrow(0, 0, nnz_c), va_c.narrow(0, 0, nnz_c)};
 }
@@ -696,12 +585,11 @@ std::tuple<Tensor, Tensor, Tensor> spgemm(Tensor roA, Tensor ciA, Tensor vaA,
     auto ci_c = torch::empty({capacity}, roA.options());
     auto va_c = torch::empty({capacity}, vaA.options());
     long long nnz_c = 0;
-    DISPATCH_FT(vaA, "spgemm", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "spgemm", (vaA), [&] {
         nnz_c = amgx_hip::spgemm_esc<scalar_t>(
-            roA.data_ptr<int>(), ciA.data_ptr<int>(), vaA.data_ptr<scalar_t>(),
-            m, ciA.numel(), roB.data_ptr<int>(), ciB.data_ptr<int>(),
-            vaB.data_ptr<scalar_t>(), k, (int)n_cols_B, ro_c.data_ptr<int>(),
-            ci_c.data_ptr<int>(), va_c.data_ptr<scalar_t>(), cur_stream());
+            iptr(roA), iptr(ciA), dptr<scalar_t>(vaA), m, ciA.numel(),
+            iptr(roB), iptr(ciB), dptr<scalar_t>(vaB), k, (int)n_cols_B,
+            iptr(ro_c), iptr(ci_c), dptr<scalar_t>(va_c), cur_stream());
     });
     return {ro_c, ci_c.narrow(0, 0, nnz_c), va_c.narrow(0, 0, nnz_c)};
 }
@@ -713,11 +601,10 @@ std::tuple<Tensor, Tensor, Tensor> transpose(Tensor ro, Tensor ci, Tensor va,
     auto ro_t = torch::empty({n_cols + 1}, ro.options());
     auto ci_t = torch::empty({nnz}, ro.options());
     auto va_t = torch::empty({nnz}, va.options());
-    DISPATCH_FT(va, "transpose", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "transpose", (va), [&] {
         amgx_hip::transpose_csr<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            m, (int)n_cols, nnz, ro_t.data_ptr<int>(), ci_t.data_ptr<int>(),
-            va_t.data_ptr<scalar_t>(), cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), m, (int)n_cols, nnz,
+            iptr(ro_t), iptr(ci_t), dptr<scalar_t>(va_t), cur_stream());
     });
     return {ro_t, ci_t, va_t};
 }
@@ -727,11 +614,10 @@ Tensor strength_ahat(Tensor ro, Tensor ci, Tensor va, Tensor didx,
                      double theta, double max_row_sum) {
     int n = (int)(ro.numel() - 1);
     auto strong = torch::empty({ci.numel()}, ro.options().dtype(torch::kUInt8));
-    DISPATCH_FT(va, "strength_ahat", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "strength_ahat", (va), [&] {
         amgx_hip::strength_ahat<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            didx.data_ptr<int>(), n, theta, max_row_sum,
-            strong.data_ptr<unsigned char>(), cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(didx), n, theta,
+            max_row_sum, dptr<unsigned char>(strong), cur_stream());
     });
     return strong;
 }
@@ -745,21 +631,18 @@ Tensor pmis_select(Tensor ro, Tensor ci, Tensor tidx, Tensor strong,
     auto state_out = torch::zeros_like(state);
     auto counter = torch::zeros({1}, ro.options().dtype(torch::kInt32));
     hipStream_t st = cur_stream();
-    amgx_hip::pmis_lambda(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                          tidx.data_ptr<int>(),
-                          strong.data_ptr<unsigned char>(), n,
-                          w.data_ptr<float>(), st);
-    amgx_hip::pmis_mark_isolated(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                                 tidx.data_ptr<int>(),
-                                 strong.data_ptr<unsigned char>(), n,
-                                 (signed char*)state.data_ptr(), st);
+    amgx_hip::pmis_lambda(iptr(ro), iptr(ci), iptr(tidx),
+                          dptr<unsigned char>(strong), n, dptr<float>(w), st);
+    amgx_hip::pmis_mark_isolated(iptr(ro), iptr(ci), iptr(tidx),
+                                 dptr<unsigned char>(strong), n,
+                                 dptr<signed char>(state), st);
     for (int round = 0; round < max_rounds; ++round) {
         counter.zero_();
         amgx_hip::pmis_one_round(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), tidx.data_ptr<int>(),
-            strong.data_ptr<unsigned char>(), n, w.data_ptr<float>(),
-            (signed char*)state.data_ptr(), (signed char*)state_mid.data_ptr(),
-            (signed char*)state_out.data_ptr(), counter.data_ptr<int>(), st);
+            iptr(ro), iptr(ci), iptr(tidx), dptr<unsigned char>(strong), n,
+            dptr<float>(w), dptr<signed char>(state),
+            dptr<signed char>(state_mid), dptr<signed char>(state_out),
+            iptr(counter), st);
         std::swap(state, state_out);
         if (counter.cpu().item<int>() == 0) break;
     }
@@ -773,13 +656,11 @@ std::tuple<Tensor, Tensor, Tensor> interp_d1(Tensor ro, Tensor ci, Tensor va,
     int n = (int)(ro.numel() - 1);
     auto p_ci = torch::empty({p_nnz}, ro.options());
     auto p_va = torch::empty({p_nnz}, va.options());
-    DISPATCH_FT(va, "interp_d1", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "interp_d1", (va), [&] {
         amgx_hip::interp_d1<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            strong.data_ptr<unsigned char>(), cf.data_ptr<int>(),
-            didx.data_ptr<int>(), p_ro.data_ptr<int>(), n,
-            (int)cf.numel(), p_ci.data_ptr<int>(),
-            p_va.data_ptr<scalar_t>(), cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va),
+            dptr<unsigned char>(strong), iptr(cf), iptr(didx), iptr(p_ro), n,
+            (int)cf.numel(), iptr(p_ci), dptr<scalar_t>(p_va), cur_stream());
     });
     return {p_ro, p_ci, p_va};
 }
@@ -789,11 +670,10 @@ std::tuple<Tensor, Tensor, Tensor> truncate_rows(Tensor ro, Tensor ci,
                                                  int64_t max_elem) {
     int n = (int)(ro.numel() - 1);
     auto counts = torch::empty({n}, ro.options());
-    DISPATCH_FT(va, "truncate_count", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "truncate_count", (va), [&] {
         amgx_hip::truncate_rows_gpu<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            n, factor, (int)max_elem, nullptr, nullptr, nullptr,
-            counts.data_ptr<int>(), cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), n, factor, (int)max_elem,
+            nullptr, nullptr, nullptr, iptr(counts), cur_stream());
     });
     auto ro_out = torch::zeros({n + 1}, ro.options());
     ro_out.slice(0, 1, n + 1).copy_(
@@ -801,12 +681,10 @@ std::tuple<Tensor, Tensor, Tensor> truncate_rows(Tensor ro, Tensor ci,
     int64_t nnz_out = n > 0 ? ro_out[n].item<int64_t>() : 0;
     auto ci_out = torch::empty({nnz_out}, ro.options());
     auto va_out = torch::empty({nnz_out}, va.options());
-    DISPATCH_FT(va, "truncate_fill", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "truncate_fill", (va), [&] {
         amgx_hip::truncate_fill_gpu<scalar_t>(
-            ro.data_ptr<int>(), ci.data_ptr<int>(), va.data_ptr<scalar_t>(),
-            n, factor, (int)max_elem, ro_out.data_ptr<int>(),
-            ci_out.data_ptr<int>(), va_out.data_ptr<scalar_t>(),
-            cur_stream());
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), n, factor, (int)max_elem,
+            iptr(ro_out), iptr(ci_out), dptr<scalar_t>(va_out), cur_stream());
     });
     return {ro_out, ci_out, va_out};
 }
@@ -814,10 +692,9 @@ std::tuple<Tensor, Tensor, Tensor> truncate_rows(Tensor ro, Tensor ci,
 Tensor interp_d1_count(Tensor ro, Tensor ci, Tensor strong, Tensor cf) {
     int n = (int)(ro.numel() - 1);
     auto counts = torch::empty({n}, ro.options());
-    amgx_hip::interp_d1_count(ro.data_ptr<int>(), ci.data_ptr<int>(),
-                              strong.data_ptr<unsigned char>(),
-                              cf.data_ptr<int>(), n, (int)cf.numel(),
-                              counts.data_ptr<int>(), cur_stream());
+    amgx_hip::interp_d1_count(iptr(ro), iptr(ci), dptr<unsigned char>(strong),
+                              iptr(cf), n, (int)cf.numel(), iptr(counts),
+                              cur_stream());
     return counts;
 }
 
@@ -826,12 +703,12 @@ Tensor ilu0_setup(Tensor ro, Tensor ci, Tensor va, Tensor didx, Tensor pos,
                   Tensor rows_sorted, std::vector<int64_t> bounds) {
     int n = (int)(ro.numel() - 1);
     auto lu = va.clone();
-    DISPATCH_FT(va, "ilu0_setup", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "ilu0_setup", (va), [&] {
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_factor_color_launch<scalar_t>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), lu.data_ptr<scalar_t>(), n, cur_stream());
+                iptr(ro), iptr(ci), iptr(pos), iptr(didx),
+                iptr(rows_sorted) + s, (int)(e - s), dptr<scalar_t>(lu), n,
+                cur_stream());
         });
     });
     return lu;
@@ -845,18 +722,16 @@ std::vector<Tensor> ilu0_setup_block(Tensor ro, Tensor ci, Tensor va,
     int n = (int)(ro.numel() - 1);
     auto lu = va.clone().reshape({-1});
     auto dinv = torch::zeros({(int64_t)n * b * b}, va.options());
-    DISPATCH_FT(va, "ilu0_setup_block", [&] {
+    DISPATCH(AMGX_REAL_TYPES, "ilu0_setup_block", (va), [&] {
         hipStream_t st = cur_stream();
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_factor_color_block_launch<scalar_t>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), lu.data_ptr<scalar_t>(),
-                dinv.data_ptr<scalar_t>(), n, (int)b, st);
+                iptr(ro), iptr(ci), iptr(pos), iptr(didx),
+                iptr(rows_sorted) + s, (int)(e - s), dptr<scalar_t>(lu),
+                dptr<scalar_t>(dinv), n, (int)b, st);
             amgx_hip::ilu0_invert_diag_block_launch<scalar_t>(
-                didx.data_ptr<int>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), lu.data_ptr<scalar_t>(),
-                dinv.data_ptr<scalar_t>(), (int)b, st);
+                iptr(didx), iptr(rows_sorted) + s, (int)(e - s),
+                dptr<scalar_t>(lu), dptr<scalar_t>(dinv), (int)b, st);
         });
     });
     return {lu, dinv};
@@ -869,26 +744,22 @@ void ilu0_apply_block(Tensor ro, Tensor ci, Tensor lu, Tensor dinv,
     int n = (int)(ro.numel() - 1);
     y.zero_();
     z.zero_();
-    DISPATCH_FT2(lu, x, "ilu0_apply_block", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "ilu0_apply_block", (lu, x), [&] {
         hipStream_t st = cur_stream();
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_fwd_block_launch<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                lu.data_ptr<scalar_a>(), rows_sorted.data_ptr<int>() + s,
-                (int)(e - s), r.data_ptr<scalar_v>(),
-                y.data_ptr<scalar_v>(), n, (int)b, st);
+                iptr(ro), iptr(ci), iptr(pos), dptr<scalar_a>(lu),
+                iptr(rows_sorted) + s, (int)(e - s), dptr<scalar_v>(r),
+                dptr<scalar_v>(y), n, (int)b, st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_bwd_block_launch<scalar_a, scalar_v>(
-                ro.data_ptr<int>(), ci.data_ptr<int>(), pos.data_ptr<int>(),
-                lu.data_ptr<scalar_a>(), dinv.data_ptr<scalar_a>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                y.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), n, (int)b,
-                st);
+                iptr(ro), iptr(ci), iptr(pos), dptr<scalar_a>(lu),
+                dptr<scalar_a>(dinv), iptr(rows_sorted) + s, (int)(e - s),
+                dptr<scalar_v>(y), dptr<scalar_v>(z), n, (int)b, st);
         });
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
+        amgx_hip::axpy<scalar_v>(dptr<scalar_v>(x), dptr<scalar_v>(z),
+                                 (scalar_v)relax, x.numel(), st);
     });
 }
 
@@ -900,26 +771,22 @@ void ilu0_apply_sorted(Tensor ro_s, Tensor ci_s, Tensor lu_s, Tensor diag_s,
     int n = (int)(ro_s.numel() - 1);
     y.zero_();
     z.zero_();
-    DISPATCH_FT2(lu_s, x, "ilu0_apply_sorted", [&] {
+    DISPATCH(AMGX_REAL_PAIRS, "ilu0_apply_sorted", (lu_s, x), [&] {
         hipStream_t st = cur_stream();
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_fwd_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                lu_s.data_ptr<scalar_a>(), pos.data_ptr<int>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                r.data_ptr<scalar_v>(), y.data_ptr<scalar_v>(), n, st);
+                iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(lu_s), iptr(pos),
+                iptr(rows_sorted) + s, (int)(e - s), dptr<scalar_v>(r),
+                dptr<scalar_v>(y), n, st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::ilu0_bwd_sorted<scalar_a, scalar_v>(
-                ro_s.data_ptr<int>() + s, ci_s.data_ptr<int>(),
-                lu_s.data_ptr<scalar_a>(),
-                diag_s.data_ptr<scalar_a>() + s, pos.data_ptr<int>(),
-                rows_sorted.data_ptr<int>() + s, (int)(e - s),
-                y.data_ptr<scalar_v>(), z.data_ptr<scalar_v>(), n, st);
+                iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(lu_s),
+                dptr<scalar_a>(diag_s) + s, iptr(pos), iptr(rows_sorted) + s,
+                (int)(e - s), dptr<scalar_v>(y), dptr<scalar_v>(z), n, st);
         });
-        amgx_hip::axpy<scalar_v>(x.data_ptr<scalar_v>(),
-                                 z.data_ptr<scalar_v>(), (scalar_v)relax,
-                                 x.numel(), st);
+        amgx_hip::axpy<scalar_v>(dptr<scalar_v>(x), dptr<scalar_v>(z),
+                                 (scalar_v)relax, x.numel(), st);
     });
 }
 

@@ -9,20 +9,42 @@
 
 #include "cplx.h"
 
+// ---- type lists ------------------------------------------------------------
+// The one statement of which types the library is built for. The explicit
+// instantiations at the end of each .hip file and the dispatch of
+// bindings.cpp both expand these lists, so a launcher cannot be dispatched
+// for a type it is not instantiated for. X is applied to each entry.
+// Pairs are (TA, TV) = (matrix-value type, vector type): the reference's
+// value modes dDDI, dFFI, dDFI and, complex, dZZI, dCCI, dZCI.
+#define AMGX_REAL_TYPES(X) X(double) X(float)
+#define AMGX_VALUE_TYPES(X) AMGX_REAL_TYPES(X) X(cplx<double>) X(cplx<float>)
+#define AMGX_REAL_PAIRS(X) X(double, double) X(float, float) X(float, double)
+#define AMGX_VALUE_PAIRS(X)                                                   \
+    AMGX_REAL_PAIRS(X)                                                        \
+    X(cplx<double>, cplx<double>)                                             \
+    X(cplx<float>, cplx<float>)                                               \
+    X(cplx<float>, cplx<double>)
+
+// explicit instantiation of launcher F for one list entry; the signature is
+// taken from the declaration below, so it is written once per .hip file
+#define AMGX_INSTANTIATE(F, ...) template decltype(F<__VA_ARGS__>) F<__VA_ARGS__>;
+
 namespace amgx_hip {
 
-// ---- SpMV family (csrmv.hip) ------------------------------------------------
-// Mixed precision: TA = matrix-value type, TV = vector type (reference dDFI);
-// instantiated for (d,d), (f,f), (f,d) and, csrmv and jacobi_smooth only,
-// for the complex pairs (cplx<double>, cplx<double>), (cplx<float>,
-// cplx<float>), (cplx<float>, cplx<double>) — reference dZZI / dCCI / dZCI.
+// ============================================================ kernels_solve.hip
+// Launchers marked [value] are instantiated over the value types or value
+// pairs (real and complex); all others over the real lists only.
+
+// ---- SpMV family -----------------------------------------------------------
+// Mixed precision: TA = matrix-value type, TV = vector type. [value]
 // y[i] = alpha * (A x)[i] + beta * y[i] + gamma * b[i]  over rows [r0, r1)
 template <typename TA, typename TV>
 void csrmv(const int* ro, const int* ci, const TA* va, const TV* x, TV* y,
            const TV* bvec, TV alpha, TV beta, TV gamma, int r0, int r1,
            double avg_deg, hipStream_t s);
 
-// block-CSR variant, block_dim b in [2,8]; values (nnz, b, b) row-major
+// block-CSR variant; values (nnz, b, b) row-major. b == 4 and b in [2,8] run
+// the wave kernels of kernels_mfma.hip, larger b bsrmv_generic
 template <typename TA, typename TV>
 void bsrmv(const int* ro, const int* ci, const TA* va, int b, const TV* x,
            TV* y, const TV* bvec, TV alpha, TV beta, TV gamma, int r0, int r1,
@@ -34,20 +56,55 @@ void bsrmv_generic(const int* ro, const int* ci, const TA* va, int b,
                    const TV* x, TV* y, const TV* bvec, TV alpha, TV beta,
                    TV gamma, int r0, int r1, hipStream_t s);
 
-// ---- LDS-hash SpGEMM (kernels_spgemm.hip) -----------------------------------
-// mode 0: C = A*B.  mode 1: aggregation Galerkin — A = aggregate-membership
-// CSR (coarse row -> fine rows), B = fine matrix, key = aggcol[col].
-// Returns nnz(C), or -1 when a row exceeds the big-table capacity (caller
-// falls back to the ESC sort path), or -2 when cap_nnz is too small.
-// big_rows_out (device, caller frees via free_device_buf) lists rows whose
-// entries were written UNSORTED (caller sorts those columns).
+// ---- BLAS-1 ----------------------------------------------------------------
+// Deterministic two-stage reduction over a fixed tree. [value]
+// op 0 = sum conj(x) y (the plain dot for real T), 1 = sum|x|, 2 = max|x|,
+// 3 = sum|x|^2; any other op throws. out (device scalar) and ws (device
+// scratch of >= 2048 elements) are of the partial type: T for op 0,
+// real_of<T> for ops 1 to 3. y is read by op 0 only.
 template <typename T>
-long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
-                      const int* roB, const int* ciB, const T* vaB,
-                      const int* aggcol, int mode, int cap0, int* roC_out,
-                      int* ciC_cap_buf, T* vaC_cap_buf, long long cap_nnz,
-                      int** big_rows_out, int* n_big_out, hipStream_t s);
-void free_device_buf(void* p, hipStream_t s);
+void reduce(const T* x, const T* y, long long n, int op, void* ws, void* out,
+            hipStream_t s);
+
+// axpy / axpby / scal: [value]; axpy_dalpha and scal_drsqrt are real-only.
+template <typename T>
+void axpy(T* y, const T* x, T a, long long n, hipStream_t s);
+template <typename T>
+void axpy_dalpha(T* y, const T* x, const T* alpha, T scale, long long n,
+                 hipStream_t s);
+template <typename T>
+void scal_drsqrt(T* x, const T* s2, long long n, hipStream_t s);
+template <typename T>
+void axpby(T* y, const T* x, T a, T b, long long n, hipStream_t s);
+template <typename T>
+void scal(T* x, T a, long long n, hipStream_t s);
+
+// ---- structure -------------------------------------------------------------
+void diag_index(const int* ro, const int* ci, int n, int* out, hipStream_t s);
+// [value]
+template <typename T>
+void extract_diag(const T* va, const int* didx, int n, int b, T* out,
+                  hipStream_t s);
+void trans_index(const int* ro, const int* ci, int n, int* out, hipStream_t s);
+
+// ---- smoothers -------------------------------------------------------------
+// inverse (block) diagonal, d == 0 gives 1; l1 adds the off-diagonal row sum
+// of |a_ij| (ro is read only then). [value]: complex T is scalar and plain
+// only, b > 1 or l1 throws.
+template <typename T>
+void jacobi_dinv(const int* ro, const T* va, const int* didx, int n, int b,
+                 bool l1, T* dinv, hipStream_t s);
+// xo = xi + omega * dinv * (b - A xi)   (block-aware; b=1 scalar fast path).
+// [value]
+template <typename TA, typename TV>
+void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
+                   const TV* bvec, const TV* xi, TV* xo, TV omega, int n,
+                   int b, hipStream_t s);
+// in-place GS update of rows[count]: x[r] += omega*dinv[r]*(b - A x)[r]
+template <typename TA, typename TV>
+void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
+                    const TA* dinv, const TV* bvec, TV* x, const int* rows,
+                    int count, TV omega, int n, int b, hipStream_t s);
 
 // ---- color-sorted sweeps (reorder-by-color layout) -------------------------
 // Matrix arrays are the rows_sorted-gathered copy, so each color reads one
@@ -85,8 +142,36 @@ template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s);
+// Einv of the rows of one color (colors ascending)
+template <typename T>
+void dilu_setup_color(const int* ro, const int* ci, const T* va,
+                      const int* didx, const int* tidx, const int* colors,
+                      const int* rows, int count, int color, T* einv, int b,
+                      hipStream_t s);
 
-// ---- MFMA wave-structured block-4 kernels (kernels_mfma.hip) ----------------
+// ---- transfer operators ----------------------------------------------------
+template <typename T>
+void restrict_agg(const T* r, const int* agg, int n, int b, T* rc,
+                  hipStream_t s);
+// deterministic variant over the aggregate-CSR structure
+template <typename T>
+void restrict_csr(const int* off, const int* fids, const T* r, int nc, int b,
+                  T* rc, hipStream_t s);
+template <typename T>
+void prolongate_agg(T* x, const T* xc, const int* agg, int n, int b,
+                    hipStream_t s);
+
+// ---- dense coarse solve ----------------------------------------------------
+template <typename TA, typename TV>
+void dense_gemv(const TA* Ainv, const TV* b, TV* x, int n, hipStream_t s);
+
+// ---- gather for halo pack --------------------------------------------------
+template <typename T>
+void gather(const T* src, const int* idx, int count, int b, T* dst,
+            hipStream_t s);
+
+// ============================================================ kernels_mfma.hip
+// MFMA wave-structured block kernels
 // v_mfma_f64_4x4x4_4b_f64 path: wave = 4 rows x 16 lanes, coalesced block
 // loads; used automatically by the b==4 dispatch of bsrmv/dilu_* above.
 void mfma4_probe(const double* a, const double* b, double* c, hipStream_t s);
@@ -113,78 +198,14 @@ void dilu_setup_b4(const int* ro, const int* ci, const TA* va,
                    const int* rows, int count, int color, TA* einv,
                    hipStream_t s);
 
-// ---- BLAS-1 (blas.hip) ------------------------------------------------------
-// op: 0 = dot(x,y), 1 = sum|x| (L1), 2 = max|x| (Lmax). Deterministic
-// two-stage reduction; out is a device scalar, ws a device scratch of
-// >= 2048 T.
-template <typename T>
-void reduce(const T* x, const T* y, long long n, int op, T* ws, T* out,
-            hipStream_t s);
-
-// complex reductions, same fixed two-stage tree. reduce_cdot: sum conj(x) y.
-// reduce_cabs: op 1 = sum|x|, 2 = max|x|, 3 = sum|x|^2, all accumulated and
-// returned in the real type R; ws as above.
-template <typename R>
-void reduce_cdot(const cplx<R>* x, const cplx<R>* y, long long n, cplx<R>* ws,
-                 cplx<R>* out, hipStream_t s);
-template <typename R>
-void reduce_cabs(const cplx<R>* x, long long n, int op, R* ws, R* out,
-                 hipStream_t s);
-
-// axpy / axpby / scal / extract_diag are also instantiated for cplx<float>
-// and cplx<double>; axpy_dalpha and scal_drsqrt are real-only.
-template <typename T>
-void axpy(T* y, const T* x, T a, long long n, hipStream_t s);
-template <typename T>
-void axpy_dalpha(T* y, const T* x, const T* alpha, T scale, long long n,
-                 hipStream_t s);
-template <typename T>
-void scal_drsqrt(T* x, const T* s2, long long n, hipStream_t s);
-template <typename T>
-void axpby(T* y, const T* x, T a, T b, long long n, hipStream_t s);
-template <typename T>
-void scal(T* x, T a, long long n, hipStream_t s);
-
-// ---- structure (misc.hip) ---------------------------------------------------
-void diag_index(const int* ro, const int* ci, int n, int* out, hipStream_t s);
-template <typename T>
-void extract_diag(const int* ro, const int* ci, const T* va, const int* didx,
-                  int n, int b, T* out, hipStream_t s);
-void trans_index(const int* ro, const int* ci, int n, int nnz, int* out,
-                 hipStream_t s);
-
-// ---- smoothers (smoothers.hip) ---------------------------------------------
-template <typename T>
-void jacobi_dinv(const int* ro, const int* ci, const T* va, const int* didx,
-                 int n, int b, bool l1, T* dinv, hipStream_t s);
-// scalar 1/d without the l1 term (complex modes; |d| == 0 gives 1)
-template <typename T>
-void jacobi_dinv_plain(const T* va, const int* didx, int n, T* dinv,
-                       hipStream_t s);
-// xo = xi + omega * dinv * (b - A xi)   (block-aware; b=1 scalar fast path)
-template <typename TA, typename TV>
-void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
-                   const TV* bvec, const TV* xi, TV* xo, TV omega, int n,
-                   int b, double avg_deg, hipStream_t s);
-// in-place GS update of rows[count]: x[r] += omega*dinv[r]*(b - A x)[r]
-template <typename TA, typename TV>
-void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
-                    const TA* dinv, const TV* bvec, TV* x, const int* rows,
-                    int count, TV omega, int n, int b, hipStream_t s);
-
-// ---- DILU (dilu.hip) --------------------------------------------------------
-template <typename T>
-void dilu_setup_color(const int* ro, const int* ci, const T* va,
-                      const int* didx, const int* tidx, const int* colors,
-                      const int* rows, int count, int color, T* einv, int b,
-                      hipStream_t s);
-// ---- coloring (setup.hip) ---------------------------------------------------
+// ============================================================ kernels_setup.hip
+// ---- coloring --------------------------------------------------------------
 // one min-max hash round; returns (via counter) number newly colored.
 void color_minmax_round(const int* ro, const int* ci, int n,
                         const int* colors_prev, int* colors_next, int iter,
                         int seed, int mode, int* n_uncolored, hipStream_t s);
 
-// ---- aggregation (setup.hip) ------------------------------------------------
+// ---- aggregation -----------------------------------------------------------
 template <typename T>
 void agg_propose(const int* ro, const int* ci, const T* va, const int* tidx,
                  const T* diag, int n, const int* agg, int* prop, int seed,
@@ -195,27 +216,7 @@ void agg_merge_singletons(const int* ro, const int* ci, const T* va,
                           const int* tidx, const T* diag, int n,
                           const int* agg_in, int* agg_out, hipStream_t s);
 
-// ---- transfer operators (misc.hip) ------------------------------------------
-template <typename T>
-void restrict_agg(const T* r, const int* agg, int n, int b, T* rc,
-                  hipStream_t s);
-// deterministic variant over the aggregate-CSR structure
-template <typename T>
-void restrict_csr(const int* off, const int* fids, const T* r, int nc, int b,
-                  T* rc, hipStream_t s);
-template <typename T>
-void prolongate_agg(T* x, const T* xc, const int* agg, int n, int b,
-                    hipStream_t s);
-
-// ---- dense coarse solve (misc.hip) -------------------------------------------
-template <typename TA, typename TV>
-void dense_gemv(const TA* Ainv, const TV* b, TV* x, int n, hipStream_t s);
-
-// ---- gather for halo pack (misc.hip) -----------------------------------------
-template <typename T>
-void gather(const T* src, const int* idx, int count, int b, T* dst,
-            hipStream_t s);
-// ---- SpGEMM / Galerkin (kernels_setup.hip) ----------------------------------
+// ---- SpGEMM / Galerkin -----------------------------------------------------
 // Aggregation Galerkin: COO keys agg[i]*nc+agg[j] -> radix sort ->
 // reduce_by_key -> CSR. Returns nnz_c; fills ro_c (nc+1); ci_c/va_c are
 // caller-allocated at worst case nnz (nnz_c <= nnz) and trimmed after.
@@ -246,7 +247,24 @@ void transpose_csr(const int* ro, const int* ci, const T* va, int m, int n,
                    long long nnz, int* ro_t, int* ci_t, T* va_t,
                    hipStream_t s);
 
-// ---- classical setup (kernels_classical.hip) --------------------------------
+// ============================================================ kernels_spgemm.hip
+// LDS-hash SpGEMM
+// mode 0: C = A*B.  mode 1: aggregation Galerkin — A = aggregate-membership
+// CSR (coarse row -> fine rows), B = fine matrix, key = aggcol[col].
+// Returns nnz(C), or -1 when a row exceeds the big-table capacity (caller
+// falls back to the ESC sort path), or -2 when cap_nnz is too small.
+// big_rows_out (device, caller frees via free_device_buf) lists rows whose
+// entries were written UNSORTED (caller sorts those columns).
+template <typename T>
+long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
+                      const int* roB, const int* ciB, const T* vaB,
+                      const int* aggcol, int mode, int cap0, int* roC_out,
+                      int* ciC_cap_buf, T* vaC_cap_buf, long long cap_nnz,
+                      int** big_rows_out, int* n_big_out, hipStream_t s);
+void free_device_buf(void* p, hipStream_t s);
+
+// ============================================================ kernels_classical.hip
+// ---- classical setup -------------------------------------------------------
 template <typename T>
 void strength_ahat(const int* ro, const int* ci, const T* va, const int* didx,
                    int n, double theta, double max_row_sum,
@@ -269,7 +287,7 @@ void interp_d1(const int* ro, const int* ci, const T* va,
                const int* p_ro, int n, int ncols, int* p_ci, T* p_va,
                hipStream_t s);
 
-// ---- ILU(0) (kernels_classical.hip) ------------------------------------------
+// ---- ILU(0) ----------------------------------------------------------------
 template <typename T>
 void ilu0_factor_color_launch(const int* ro, const int* ci, const int* pos,
                               const int* didx, const int* rows, int count,
@@ -305,10 +323,7 @@ void ilu0_bwd_block_launch(const int* ro, const int* ci, const int* pos,
                            int count, const TV* y, TV* z, int n, int b,
                            hipStream_t s);
 
-}  // namespace amgx_hip
-
-// ---- truncate (kernels_classical.hip) ----------------------------------------
-namespace amgx_hip {
+// ---- truncate --------------------------------------------------------------
 template <typename T>
 void truncate_rows_gpu(const int* ro, const int* ci, const T* va, int n,
                        double factor, int max_elem, const int* ro_out,

@@ -95,6 +95,22 @@ AMGX_HD cplx<R> conj_mul(const cplx<R>& a, const cplx<R>& b) {
     return cplx<R>(rr + ii, ri - ir);
 }
 
+// Real counterparts of conj_mul / abs / abs2, so one kernel template
+// (reduce_stage1) serves real and complex T. Plain products with contraction
+// left on: a real dot stays one fused multiply-add per element.
+AMGX_HD double conj_mul(double a, double b) { return a * b; }
+AMGX_HD float conj_mul(float a, float b) { return a * b; }
+AMGX_HD double abs(double a) { return std::fabs(a); }
+AMGX_HD float abs(float a) { return std::fabs(a); }
+AMGX_HD double abs2(double a) { return a * a; }
+AMGX_HD float abs2(float a) { return a * a; }
+
+template <typename T> struct is_cplx { static constexpr bool value = false; };
+template <typename R> struct is_cplx<cplx<R>> { static constexpr bool value = true; };
+// R for cplx<R>, T itself for a real T: the type of |x| and of a norm
+template <typename T> struct real_of { using type = T; };
+template <typename R> struct real_of<cplx<R>> { using type = R; };
+
 #if defined(__HIPCC__)
 // cross-lane moves of the two components (wave_reduce_sum, csrmv_vec); the
 // using-declarations keep the built-in real overloads visible to kernels

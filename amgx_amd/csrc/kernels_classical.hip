@@ -13,6 +13,7 @@
 #include <string>
 
 #include "common.h"
+#include "core_api.h"
 
 namespace amgx_hip {
 
@@ -608,56 +609,20 @@ void ilu0_factor_color_launch(const int* ro, const int* ci, const int* pos,
 }
 
 #define INSTANTIATE_CLASSICAL(T)                                               \
-    template void strength_ahat<T>(const int*, const int*, const T*,           \
-                                   const int*, int, double, double,            \
-                                   unsigned char*, hipStream_t);               \
-    template void interp_d1<T>(const int*, const int*, const T*,               \
-                               const unsigned char*, const int*, const int*,   \
-                               const int*, int, int, int*, T*, hipStream_t);   \
-    template void ilu0_factor_color_launch<T>(const int*, const int*,          \
-                                              const int*, const int*,          \
-                                              const int*, int, T*, int,        \
-                                              hipStream_t);                    \
-    template void ilu0_fwd_sorted<T, T>(const int*, const int*, const T*,      \
-                                        const int*, const int*, int,            \
-                                        const T*, T*, int, hipStream_t);        \
-    template void ilu0_bwd_sorted<T, T>(const int*, const int*, const T*,       \
-                                        const T*, const int*, const int*,        \
-                                        int, const T*, T*, int, hipStream_t);   \
-    template void ilu0_factor_color_block_launch<T>(                           \
-        const int*, const int*, const int*, const int*, const int*, int, T*,  \
-        const T*, int, int, hipStream_t);                                      \
-    template void ilu0_invert_diag_block_launch<T>(                            \
-        const int*, const int*, int, const T*, T*, int, hipStream_t);          \
-    template void ilu0_fwd_block_launch<T, T>(                                 \
-        const int*, const int*, const int*, const T*, const int*, int,         \
-        const T*, T*, int, int, hipStream_t);                                  \
-    template void ilu0_bwd_block_launch<T, T>(                                 \
-        const int*, const int*, const int*, const T*, const T*, const int*,    \
-        int, const T*, T*, int, int, hipStream_t);
+    AMGX_INSTANTIATE(strength_ahat, T)                                         \
+    AMGX_INSTANTIATE(interp_d1, T)                                             \
+    AMGX_INSTANTIATE(ilu0_factor_color_launch, T)                              \
+    AMGX_INSTANTIATE(ilu0_factor_color_block_launch, T)                        \
+    AMGX_INSTANTIATE(ilu0_invert_diag_block_launch, T)
+// ILU(0) applies: the float factor serves double vectors too (dDFI)
+#define INSTANTIATE_CLASSICAL_PAIR(TA, TV)                                     \
+    AMGX_INSTANTIATE(ilu0_fwd_sorted, TA, TV)                                  \
+    AMGX_INSTANTIATE(ilu0_bwd_sorted, TA, TV)                                  \
+    AMGX_INSTANTIATE(ilu0_fwd_block_launch, TA, TV)                            \
+    AMGX_INSTANTIATE(ilu0_bwd_block_launch, TA, TV)
 
-INSTANTIATE_CLASSICAL(double)
-INSTANTIATE_CLASSICAL(float)
-// mixed dDFI ILU apply: float factor, double vectors
-template void ilu0_fwd_sorted<float, double>(const int*, const int*,
-                                             const float*, const int*,
-                                             const int*, int, const double*,
-                                             double*, int, hipStream_t);
-template void ilu0_bwd_sorted<float, double>(const int*, const int*,
-                                             const float*, const float*,
-                                             const int*, const int*, int,
-                                             const double*, double*, int,
-                                             hipStream_t);
-template void ilu0_fwd_block_launch<float, double>(
-    const int*, const int*, const int*, const float*, const int*, int,
-    const double*, double*, int, int, hipStream_t);
-template void ilu0_bwd_block_launch<float, double>(
-    const int*, const int*, const int*, const float*, const float*,
-    const int*, int, const double*, double*, int, int, hipStream_t);
-
-}  // namespace amgx_hip
-
-namespace amgx_hip {
+AMGX_REAL_TYPES(INSTANTIATE_CLASSICAL)
+AMGX_REAL_PAIRS(INSTANTIATE_CLASSICAL_PAIR)
 
 // ============================================================ truncate
 // Drop |p_ij| < factor * rowmax_i, rescale survivors to preserve the row sum
@@ -779,14 +744,9 @@ void truncate_fill_gpu(const int* ro, const int* ci, const T* va, int n,
 }
 
 #define INSTANTIATE_TRUNC(T)                                                   \
-    template void truncate_rows_gpu<T>(const int*, const int*, const T*, int, \
-                                       double, int, const int*, int*, T*,     \
-                                       int*, hipStream_t);                    \
-    template void truncate_fill_gpu<T>(const int*, const int*, const T*, int, \
-                                       double, int, const int*, int*, T*,     \
-                                       hipStream_t);
+    AMGX_INSTANTIATE(truncate_rows_gpu, T)                                     \
+    AMGX_INSTANTIATE(truncate_fill_gpu, T)
 
-INSTANTIATE_TRUNC(double)
-INSTANTIATE_TRUNC(float)
+AMGX_REAL_TYPES(INSTANTIATE_TRUNC)
 
 }  // namespace amgx_hip

@@ -360,31 +360,14 @@ void bsrmv_bn(const int* ro, const int* ci, const TA* va, int b,
 }
 
 // ------------------------------------------------------------ instantiation
-#define INSTANTIATE_MFMA_MIXED(TA, TV)                                        \
-    template void dilu_fwd_b4_sorted<TA, TV>(const int*, const int*,          \
-                                             const TA*, const TA*,            \
-                                             const int*, int, const TV*,      \
-                                             const TV*, TV*, hipStream_t);    \
-    template void dilu_bwd_b4_sorted<TA, TV>(const int*, const int*,          \
-                                             const TA*, const TA*,            \
-                                             const int*, int, const TV*,      \
-                                             TV*, hipStream_t);               \
-    template void bsrmv_b4<TA, TV>(const int*, const int*, const TA*,         \
-                                   const TV*, TV*, const TV*, double, double, \
-                                   double, int, int, hipStream_t);            \
-    template void bsrmv_bn<TA, TV>(const int*, const int*, const TA*, int,    \
-                                   const TV*, TV*, const TV*, double, double, \
-                                   double, int, int, hipStream_t);
+#define INSTANTIATE_MFMA_PAIR(TA, TV)                                         \
+    AMGX_INSTANTIATE(dilu_fwd_b4_sorted, TA, TV)                              \
+    AMGX_INSTANTIATE(dilu_bwd_b4_sorted, TA, TV)                              \
+    AMGX_INSTANTIATE(bsrmv_b4, TA, TV)                                        \
+    AMGX_INSTANTIATE(bsrmv_bn, TA, TV)
+#define INSTANTIATE_MFMA(TA) AMGX_INSTANTIATE(dilu_setup_b4, TA)
 
-#define INSTANTIATE_MFMA(TA)                                                  \
-    template void dilu_setup_b4<TA>(const int*, const int*, const TA*,        \
-                                    const int*, const int*, const int*,       \
-                                    const int*, int, int, TA*, hipStream_t);
-
-INSTANTIATE_MFMA(double)
-INSTANTIATE_MFMA(float)
-INSTANTIATE_MFMA_MIXED(double, double)
-INSTANTIATE_MFMA_MIXED(float, float)
-INSTANTIATE_MFMA_MIXED(float, double)
+AMGX_REAL_TYPES(INSTANTIATE_MFMA)
+AMGX_REAL_PAIRS(INSTANTIATE_MFMA_PAIR)
 
 }  // namespace amgx_hip

@@ -593,25 +593,12 @@ void transpose_csr(const int* ro, const int* ci, const T* va, int m, int n,
 
 // ============================================================ instantiation
 #define INSTANTIATE_SETUP(T)                                                   \
-    template void agg_propose<T>(const int*, const int*, const T*,             \
-                                 const int*, const T*, int, const int*, int*,  \
-                                 int, hipStream_t);                            \
-    template void agg_merge_singletons<T>(const int*, const int*, const T*,    \
-                                          const int*, const T*, int,           \
-                                          const int*, int*, hipStream_t);      \
-    template long long galerkin_agg<T>(const int*, const int*, const T*, int,  \
-                                       long long, const int*, const int*, int, \
-                                       long long, int*, int*, T*, int,         \
-                                       hipStream_t);                  \
-    template long long spgemm_esc<T>(const int*, const int*, const T*, int,    \
-                                     long long, const int*, const int*,        \
-                                     const T*, int, int, int*, int*, T*,       \
-                                     hipStream_t);                             \
-    template void transpose_csr<T>(const int*, const int*, const T*, int,      \
-                                   int, long long, int*, int*, T*,             \
-                                   hipStream_t);
+    AMGX_INSTANTIATE(agg_propose, T)                                           \
+    AMGX_INSTANTIATE(agg_merge_singletons, T)                                  \
+    AMGX_INSTANTIATE(galerkin_agg, T)                                          \
+    AMGX_INSTANTIATE(spgemm_esc, T)                                            \
+    AMGX_INSTANTIATE(transpose_csr, T)
 
-INSTANTIATE_SETUP(double)
-INSTANTIATE_SETUP(float)
+AMGX_REAL_TYPES(INSTANTIATE_SETUP)
 
 }  // namespace amgx_hip

@@ -111,27 +111,6 @@ __global__ __launch_bounds__(AMGX_BLOCK) void bsrmv_kernel(const int* __restrict
     y[oi] = out;
 }
 
-template <typename TA, typename TV>
-void bsrmv(const int* ro, const int* ci, const TA* va, int b, const TV* x,
-           TV* y, const TV* bvec, TV alpha, TV beta, TV gamma, int r0, int r1,
-           hipStream_t s) {
-    long long rows = ((long long)r1 - r0) * b;
-    if (rows <= 0) return;
-    if (b == 4) {   // MFMA wave kernel (kernels_mfma.hip)
-        bsrmv_b4<TA, TV>(ro, ci, va, x, y, bvec, (double)alpha, (double)beta,
-                         (double)gamma, r0, r1, s);
-        return;
-    }
-    if (b >= 2 && b <= 8) {   // generic wave kernel, coalesced block loads
-        bsrmv_bn<TA, TV>(ro, ci, va, b, x, y, bvec, (double)alpha,
-                         (double)beta, (double)gamma, r0, r1, s);
-        return;
-    }
-    hipLaunchKernelGGL((bsrmv_kernel<TA, TV>), dim3(grid_1d(rows)),
-                       dim3(AMGX_BLOCK), 0, s, ro, ci, va, b, x, y, bvec,
-                       alpha, beta, gamma, r0, r1);
-}
-
 // baseline scalar thread-per-row-component kernel, any b (A/B comparison
 // target for the MFMA b=4 path in bench_kernels.py)
 template <typename TA, typename TV>
@@ -145,26 +124,52 @@ void bsrmv_generic(const int* ro, const int* ci, const TA* va, int b,
                        alpha, beta, gamma, r0, r1);
 }
 
+template <typename TA, typename TV>
+void bsrmv(const int* ro, const int* ci, const TA* va, int b, const TV* x,
+           TV* y, const TV* bvec, TV alpha, TV beta, TV gamma, int r0, int r1,
+           hipStream_t s) {
+    if (r1 <= r0) return;
+    if (b == 4)             // MFMA wave kernel (kernels_mfma.hip)
+        bsrmv_b4<TA, TV>(ro, ci, va, x, y, bvec, (double)alpha, (double)beta,
+                         (double)gamma, r0, r1, s);
+    else if (b >= 2 && b <= 8)   // generic wave kernel, coalesced block loads
+        bsrmv_bn<TA, TV>(ro, ci, va, b, x, y, bvec, (double)alpha,
+                         (double)beta, (double)gamma, r0, r1, s);
+    else
+        bsrmv_generic<TA, TV>(ro, ci, va, b, x, y, bvec, alpha, beta, gamma,
+                              r0, r1, s);
+}
+
 // ============================================================ BLAS-1 reduce
 // Deterministic two-stage reduction: fixed grid of NPART partials, then one
-// block folds them. op: 0 dot, 1 L1, 2 Lmax.
+// block folds them. OP 0: sum conj(x_i) y_i (x_i y_i for real T), partials of
+// type T. OP 1 sum|x_i|, OP 2 max|x_i|, OP 3 sum|x_i|^2: accumulators and
+// partials of the real type of T, so a complex squared 2-norm is exactly
+// real and non-negative.
 #define NPART 1024
 
 template <typename T, int OP>
-__global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage1(const T* __restrict__ x, const T* __restrict__ y,
-                              long long n, T* __restrict__ part) {
+using partial_t = std::conditional_t<OP == 0, T, typename real_of<T>::type>;
+
+template <typename T, int OP>
+__global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage1(
+    const T* __restrict__ x, const T* __restrict__ y, long long n,
+    partial_t<T, OP>* __restrict__ part) {
+    using A = partial_t<T, OP>;
     long long stride = (long long)gridDim.x * blockDim.x;
-    T acc = T(0);
+    A acc = A(0);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += stride) {
-        if (OP == 0) acc += x[i] * y[i];
-        else if (OP == 1) acc += fabs((double)x[i]);
-        else {
-            T a = fabs((double)x[i]);
+        if constexpr (OP == 0) acc += conj_mul(x[i], y[i]);
+        else if constexpr (OP == 1) acc += abs(x[i]);
+        else if constexpr (OP == 2) {
+            A a = abs(x[i]);
             acc = a > acc ? a : acc;
-        }
+        } else acc += abs2(x[i]);
     }
-    T r = (OP == 2) ? block_reduce_max(acc) : block_reduce_sum(acc);
+    A r;
+    if constexpr (OP == 2) r = block_reduce_max(acc);
+    else r = block_reduce_sum(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
@@ -181,90 +186,32 @@ __global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage2(const T* __restrict_
     if (threadIdx.x == 0) *out = r;
 }
 
-// Complex stage 1. OP 0: sum conj(x_i) y_i, complex partials. OP 1 sum|x_i|,
-// OP 2 max|x_i|, OP 3 sum|x_i|^2: real accumulators and real partials, so a
-// squared 2-norm is exactly real and non-negative. Stage 2 is the fold
-// above on the partial type.
-template <typename R, int OP>
-__global__ __launch_bounds__(AMGX_BLOCK) void reduce_stage1_cplx(
-    const cplx<R>* __restrict__ x, const cplx<R>* __restrict__ y, long long n,
-    std::conditional_t<OP == 0, cplx<R>, R>* __restrict__ part) {
-    using A = std::conditional_t<OP == 0, cplx<R>, R>;
-    long long stride = (long long)gridDim.x * blockDim.x;
-    A acc = A(0);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        if constexpr (OP == 0) acc += conj_mul(x[i], y[i]);
-        else if constexpr (OP == 1) acc += abs(x[i]);
-        else if constexpr (OP == 2) {
-            R a = abs(x[i]);
-            acc = a > acc ? a : acc;
-        } else acc += abs2(x[i]);
-    }
-    A r;
-    if constexpr (OP == 2) r = block_reduce_max(acc);
-    else r = block_reduce_sum(acc);
-    if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-template <typename R>
-void reduce_cdot(const cplx<R>* x, const cplx<R>* y, long long n, cplx<R>* ws,
-                 cplx<R>* out, hipStream_t s) {
+template <typename T, int OP>
+void reduce_launch(const T* x, const T* y, long long n, void* ws, void* out,
+                   hipStream_t s) {
+    using A = partial_t<T, OP>;
     int g = grid_1d(n, AMGX_BLOCK, NPART);
-    hipLaunchKernelGGL((reduce_stage1_cplx<R, 0>), dim3(g), dim3(AMGX_BLOCK),
-                       0, s, x, y, n, ws);
-    hipLaunchKernelGGL((reduce_stage2<cplx<R>, 0>), dim3(1), dim3(AMGX_BLOCK),
-                       0, s, ws, g, out);
-}
-
-template <typename R>
-void reduce_cabs(const cplx<R>* x, long long n, int op, R* ws, R* out,
-                 hipStream_t s) {
-    int g = grid_1d(n, AMGX_BLOCK, NPART);
-    const cplx<R>* none = nullptr;
-    switch (op) {
-        case 1:
-            hipLaunchKernelGGL((reduce_stage1_cplx<R, 1>), dim3(g),
-                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<R, 1>), dim3(1),
-                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
-            break;
-        case 2:
-            hipLaunchKernelGGL((reduce_stage1_cplx<R, 2>), dim3(g),
-                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<R, 2>), dim3(1),
-                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
-            break;
-        default:
-            hipLaunchKernelGGL((reduce_stage1_cplx<R, 3>), dim3(g),
-                               dim3(AMGX_BLOCK), 0, s, x, none, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<R, 1>), dim3(1),
-                               dim3(AMGX_BLOCK), 0, s, ws, g, out);
-    }
+    hipLaunchKernelGGL((reduce_stage1<T, OP>), dim3(g), dim3(AMGX_BLOCK), 0, s,
+                       x, y, n, (A*)ws);
+    // OP 3 folds its partials by the plain sum of OP 1
+    hipLaunchKernelGGL((reduce_stage2<A, OP == 3 ? 1 : OP>), dim3(1),
+                       dim3(AMGX_BLOCK), 0, s, (const A*)ws, g, (A*)out);
 }
 
 template <typename T>
-void reduce(const T* x, const T* y, long long n, int op, T* ws, T* out,
+void reduce(const T* x, const T* y, long long n, int op, void* ws, void* out,
             hipStream_t s) {
-    int g = grid_1d(n, AMGX_BLOCK, NPART);
     switch (op) {
-        case 0:
-            hipLaunchKernelGGL((reduce_stage1<T, 0>), dim3(g), dim3(AMGX_BLOCK),
-                               0, s, x, y, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<T, 0>), dim3(1), dim3(AMGX_BLOCK),
-                               0, s, ws, g, out);
-            break;
-        case 1:
-            hipLaunchKernelGGL((reduce_stage1<T, 1>), dim3(g), dim3(AMGX_BLOCK),
-                               0, s, x, y, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<T, 1>), dim3(1), dim3(AMGX_BLOCK),
-                               0, s, ws, g, out);
-            break;
+        case 0: return reduce_launch<T, 0>(x, y, n, ws, out, s);
+        case 1: return reduce_launch<T, 1>(x, y, n, ws, out, s);
+        case 2: return reduce_launch<T, 2>(x, y, n, ws, out, s);
+        case 3:   // complex only: a real squared norm is op 0 of (x, x)
+            if constexpr (is_cplx<T>::value)
+                return reduce_launch<T, 3>(x, y, n, ws, out, s);
+            [[fallthrough]];
         default:
-            hipLaunchKernelGGL((reduce_stage1<T, 2>), dim3(g), dim3(AMGX_BLOCK),
-                               0, s, x, y, n, ws);
-            hipLaunchKernelGGL((reduce_stage2<T, 2>), dim3(1), dim3(AMGX_BLOCK),
-                               0, s, ws, g, out);
+            throw std::runtime_error("reduce: unknown op " +
+                                     std::to_string(op));
     }
 }
 
@@ -391,8 +338,8 @@ __global__ __launch_bounds__(AMGX_BLOCK) void extract_diag_kernel(const T* __res
 }
 
 template <typename T>
-void extract_diag(const int* ro, const int* ci, const T* va, const int* didx,
-                  int n, int b, T* out, hipStream_t s) {
+void extract_diag(const T* va, const int* didx, int n, int b, T* out,
+                  hipStream_t s) {
     long long total = (long long)n * b * b;
     hipLaunchKernelGGL((extract_diag_kernel<T>), dim3(grid_1d(total)),
                        dim3(AMGX_BLOCK), 0, s, va, didx, n, b, out);
@@ -420,16 +367,16 @@ __global__ __launch_bounds__(AMGX_BLOCK) void trans_index_kernel(const int* __re
     }
 }
 
-void trans_index(const int* ro, const int* ci, int n, int nnz, int* out,
-                 hipStream_t s) {
+void trans_index(const int* ro, const int* ci, int n, int* out, hipStream_t s) {
     hipLaunchKernelGGL(trans_index_kernel, dim3(grid_1d(n)), dim3(AMGX_BLOCK),
                        0, s, ro, ci, n, out);
 }
 
 // ============================================================ Jacobi
+// scalar 1/d, d == 0 gives 1 as on the host. The l1 term needs fabs and a
+// sign, so it is compiled out for value types without an ordering (complex).
 template <typename T>
 __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_scalar(const int* __restrict__ ro,
-                                   const int* __restrict__ ci,
                                    const T* __restrict__ va,
                                    const int* __restrict__ didx, int n,
                                    bool l1, T* __restrict__ dinv) {
@@ -437,11 +384,13 @@ __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_scalar(const int* __re
     if (i >= n) return;
     int dk = didx[i];
     T d = dk >= 0 ? va[dk] : T(0);
-    if (l1) {
-        T sum = T(0);
-        for (int k = ro[i]; k < ro[i + 1]; ++k)
-            if (k != dk) sum += fabs((double)va[k]);
-        d += (d >= T(0) ? sum : -sum);
+    if constexpr (!is_cplx<T>::value) {
+        if (l1) {
+            T sum = T(0);
+            for (int k = ro[i]; k < ro[i + 1]; ++k)
+                if (k != dk) sum += fabs((double)va[k]);
+            d += (d >= T(0) ? sum : -sum);
+        }
     }
     if (d == T(0)) d = T(1);
     dinv[i] = T(1) / d;
@@ -449,7 +398,6 @@ __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_scalar(const int* __re
 
 template <typename T, int BMAX>
 __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_block(const int* __restrict__ ro,
-                                  const int* __restrict__ ci,
                                   const T* __restrict__ va,
                                   const int* __restrict__ didx, int n, int b,
                                   bool l1, T* __restrict__ dinv) {
@@ -475,42 +423,24 @@ __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_block(const int* __res
 }
 
 template <typename T>
-void jacobi_dinv(const int* ro, const int* ci, const T* va, const int* didx,
-                 int n, int b, bool l1, T* dinv, hipStream_t s) {
+void jacobi_dinv(const int* ro, const T* va, const int* didx, int n, int b,
+                 bool l1, T* dinv, hipStream_t s) {
+    if (is_cplx<T>::value && (b != 1 || l1))
+        throw std::runtime_error("jacobi_dinv: complex matrices support "
+                                 "neither blocks nor the l1 variant");
     if (b == 1) {
         hipLaunchKernelGGL((jacobi_dinv_scalar<T>), dim3(grid_1d(n)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, didx, n, l1,
-                           dinv);
-    } else if (b <= 8) {
-        hipLaunchKernelGGL((jacobi_dinv_block<T, 8>), dim3(grid_1d(n)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, didx, n, b, l1,
-                           dinv);
-    } else {
-        hipLaunchKernelGGL((jacobi_dinv_block<T, 16>), dim3(grid_1d(n)),
-                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, didx, n, b, l1,
-                           dinv);
+                           dim3(AMGX_BLOCK), 0, s, ro, va, didx, n, l1, dinv);
+    } else if constexpr (!is_cplx<T>::value) {
+        if (b <= 8)
+            hipLaunchKernelGGL((jacobi_dinv_block<T, 8>), dim3(grid_1d(n)),
+                               dim3(AMGX_BLOCK), 0, s, ro, va, didx, n, b, l1,
+                               dinv);
+        else
+            hipLaunchKernelGGL((jacobi_dinv_block<T, 16>), dim3(grid_1d(n)),
+                               dim3(AMGX_BLOCK), 0, s, ro, va, didx, n, b, l1,
+                               dinv);
     }
-}
-
-// plain scalar 1/d for value types without an ordering (complex modes): the
-// l1 variant above needs fabs and a sign. |d| == 0 gives 1, as on the host.
-template <typename T>
-__global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_plain_kernel(const T* __restrict__ va,
-                                         const int* __restrict__ didx, int n,
-                                         T* __restrict__ dinv) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int dk = didx[i];
-    T d = dk >= 0 ? va[dk] : T(0);
-    if (d == T(0)) d = T(1);
-    dinv[i] = T(1) / d;
-}
-
-template <typename T>
-void jacobi_dinv_plain(const T* va, const int* didx, int n, T* dinv,
-                       hipStream_t s) {
-    hipLaunchKernelGGL((jacobi_dinv_plain_kernel<T>), dim3(grid_1d(n)),
-                       dim3(AMGX_BLOCK), 0, s, va, didx, n, dinv);
 }
 
 // fused damped Jacobi sweep: xo = xi + omega*dinv*(b - A xi), single pass.
@@ -563,7 +493,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_smooth_block(const int* __r
 template <typename TA, typename TV>
 void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
                    const TV* bvec, const TV* xi, TV* xo, TV omega, int n,
-                   int b, double avg_deg, hipStream_t s) {
+                   int b, hipStream_t s) {
     if (b == 1) {
         hipLaunchKernelGGL((jacobi_smooth_scalar<TA, TV>), dim3(grid_1d(n)),
                            dim3(AMGX_BLOCK), 0, s, ro, ci, va, dinv, bvec, xi,
@@ -1159,109 +1089,40 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
 }
 
 // ============================================================ instantiation
-// vector-typed ops (single type)
-#define INSTANTIATE(T)                                                          \
-    template void reduce<T>(const T*, const T*, long long, int, T*, T*,         \
-                            hipStream_t);                                       \
-    template void axpy<T>(T*, const T*, T, long long, hipStream_t);             \
-    template void axpy_dalpha<T>(T*, const T*, const T*, T, long long,          \
-                                 hipStream_t);                                  \
-    template void scal_drsqrt<T>(T*, const T*, long long, hipStream_t);         \
-    template void axpby<T>(T*, const T*, T, T, long long, hipStream_t);         \
-    template void scal<T>(T*, T, long long, hipStream_t);                       \
-    template void extract_diag<T>(const int*, const int*, const T*,             \
-                                  const int*, int, int, T*, hipStream_t);       \
-    template void jacobi_dinv<T>(const int*, const int*, const T*, const int*,  \
-                                 int, int, bool, T*, hipStream_t);              \
-    template void dilu_setup_color<T>(const int*, const int*, const T*,         \
-                                      const int*, const int*, const int*,       \
-                                      const int*, int, int, T*, int,            \
-                                      hipStream_t);                             \
-    template void restrict_agg<T>(const T*, const int*, int, int, T*,           \
-                                  hipStream_t);                                 \
-    template void restrict_csr<T>(const int*, const int*, const T*, int, int,   \
-                                  T*, hipStream_t);                             \
-    template void prolongate_agg<T>(T*, const T*, const int*, int, int,         \
-                                    hipStream_t);                               \
-    template void gather<T>(const T*, const int*, int, int, T*, hipStream_t);
+// over the type lists of core_api.h; complex types get the Krylov + Jacobi
+// subset (scalar CSR), whose template bodies are the real ones
+#define INSTANTIATE_REAL(T)                                                     \
+    AMGX_INSTANTIATE(axpy_dalpha, T)                                            \
+    AMGX_INSTANTIATE(scal_drsqrt, T)                                            \
+    AMGX_INSTANTIATE(dilu_setup_color, T)                                       \
+    AMGX_INSTANTIATE(restrict_agg, T)                                           \
+    AMGX_INSTANTIATE(restrict_csr, T)                                           \
+    AMGX_INSTANTIATE(prolongate_agg, T)                                         \
+    AMGX_INSTANTIATE(gather, T)
+#define INSTANTIATE_VALUE(T)                                                    \
+    AMGX_INSTANTIATE(reduce, T)                                                 \
+    AMGX_INSTANTIATE(axpy, T)                                                   \
+    AMGX_INSTANTIATE(axpby, T)                                                  \
+    AMGX_INSTANTIATE(scal, T)                                                   \
+    AMGX_INSTANTIATE(extract_diag, T)                                           \
+    AMGX_INSTANTIATE(jacobi_dinv, T)
+#define INSTANTIATE_REAL_PAIR(TA, TV)                                           \
+    AMGX_INSTANTIATE(bsrmv, TA, TV)                                             \
+    AMGX_INSTANTIATE(bsrmv_generic, TA, TV)                                     \
+    AMGX_INSTANTIATE(dilu_small, TA, TV)                                        \
+    AMGX_INSTANTIATE(dilu_fwd_sorted, TA, TV)                                   \
+    AMGX_INSTANTIATE(dilu_bwd_sorted, TA, TV)                                   \
+    AMGX_INSTANTIATE(gs_sweep_small, TA, TV)                                    \
+    AMGX_INSTANTIATE(gs_rows_sorted, TA, TV)                                    \
+    AMGX_INSTANTIATE(gs_smooth_rows, TA, TV)                                    \
+    AMGX_INSTANTIATE(dense_gemv, TA, TV)
+#define INSTANTIATE_VALUE_PAIR(TA, TV)                                          \
+    AMGX_INSTANTIATE(csrmv, TA, TV)                                             \
+    AMGX_INSTANTIATE(jacobi_smooth, TA, TV)
 
-// matrix-value x vector mixed ops: (TA, TV) in {(d,d), (f,f), (f,d)} — the
-// reference's dDDI / dFFI / dDFI value modes
-#define INSTANTIATE_MIXED(TA, TV)                                               \
-    template void csrmv<TA, TV>(const int*, const int*, const TA*, const TV*,   \
-                                TV*, const TV*, TV, TV, TV, int, int, double,   \
-                                hipStream_t);                                   \
-    template void bsrmv<TA, TV>(const int*, const int*, const TA*, int,         \
-                                const TV*, TV*, const TV*, TV, TV, TV, int,     \
-                                int, hipStream_t);                              \
-    template void bsrmv_generic<TA, TV>(const int*, const int*, const TA*,      \
-                                        int, const TV*, TV*, const TV*, TV,     \
-                                        TV, TV, int, int, hipStream_t);         \
-    template void jacobi_smooth<TA, TV>(const int*, const int*, const TA*,      \
-                                        const TA*, const TV*, const TV*, TV*,   \
-                                        TV, int, int, double, hipStream_t);     \
-    template void dilu_small<TA, TV>(const int*, const int*, const TA*,         \
-                                     const TA*, const int*, const int*, int,    \
-                                     const TV*, TV*, TV*, TV*, TV, long long,   \
-                                     bool, hipStream_t);                        \
-    template void dilu_fwd_sorted<TA, TV>(const int*, const int*, const TA*,    \
-                                          const TA*, const int*, int,           \
-                                          const TV*, const TV*, TV*, int,       \
-                                          hipStream_t);                         \
-    template void dilu_bwd_sorted<TA, TV>(const int*, const int*, const TA*,    \
-                                          const TA*, const int*, int,           \
-                                          const TV*, TV*, int, hipStream_t);    \
-    template void gs_sweep_small<TA, TV>(const int*, const int*, const TA*,     \
-                                         const TA*, const TV*, TV*,             \
-                                         const int*, const int*, int, TV,       \
-                                         bool, hipStream_t);                    \
-    template void gs_rows_sorted<TA, TV>(const int*, const int*, const TA*,     \
-                                         const TA*, const TV*, TV*,             \
-                                         const int*, int, TV, hipStream_t);     \
-    template void gs_smooth_rows<TA, TV>(const int*, const int*, const TA*,     \
-                                         const TA*, const TV*, TV*,             \
-                                         const int*, int, TV, int, int,         \
-                                         hipStream_t);                          \
-    template void dense_gemv<TA, TV>(const TA*, const TV*, TV*, int,            \
-                                     hipStream_t);
-
-INSTANTIATE(double)
-INSTANTIATE(float)
-INSTANTIATE_MIXED(double, double)
-INSTANTIATE_MIXED(float, float)
-INSTANTIATE_MIXED(float, double)
-
-// complex modes dZZI / dCCI / dZCI: the Krylov + Jacobi subset, scalar CSR.
-// The template bodies are the real ones; sweeps, setup and transfer kernels
-// get no complex instantiation.
-#define INSTANTIATE_CPLX(R)                                                     \
-    template void reduce_cdot<R>(const cplx<R>*, const cplx<R>*, long long,     \
-                                 cplx<R>*, cplx<R>*, hipStream_t);              \
-    template void reduce_cabs<R>(const cplx<R>*, long long, int, R*, R*,        \
-                                 hipStream_t);                                  \
-    template void axpy<cplx<R>>(cplx<R>*, const cplx<R>*, cplx<R>, long long,   \
-                                hipStream_t);                                   \
-    template void axpby<cplx<R>>(cplx<R>*, const cplx<R>*, cplx<R>, cplx<R>,    \
-                                 long long, hipStream_t);                       \
-    template void scal<cplx<R>>(cplx<R>*, cplx<R>, long long, hipStream_t);     \
-    template void extract_diag<cplx<R>>(const int*, const int*,                 \
-                                        const cplx<R>*, const int*, int, int,   \
-                                        cplx<R>*, hipStream_t);                 \
-    template void jacobi_dinv_plain<cplx<R>>(const cplx<R>*, const int*, int,   \
-                                             cplx<R>*, hipStream_t);
-
-#define INSTANTIATE_CPLX_MIXED(TA, TV)                                          \
-    template void csrmv<TA, TV>(const int*, const int*, const TA*, const TV*,   \
-                                TV*, const TV*, TV, TV, TV, int, int, double,   \
-                                hipStream_t);                                   \
-    template void jacobi_smooth<TA, TV>(const int*, const int*, const TA*,      \
-                                        const TA*, const TV*, const TV*, TV*,   \
-                                        TV, int, int, double, hipStream_t);
-
-INSTANTIATE_CPLX(double)
-INSTANTIATE_CPLX(float)
-INSTANTIATE_CPLX_MIXED(cplx<double>, cplx<double>)
-INSTANTIATE_CPLX_MIXED(cplx<float>, cplx<float>)
-INSTANTIATE_CPLX_MIXED(cplx<float>, cplx<double>)
+AMGX_REAL_TYPES(INSTANTIATE_REAL)
+AMGX_VALUE_TYPES(INSTANTIATE_VALUE)
+AMGX_REAL_PAIRS(INSTANTIATE_REAL_PAIR)
+AMGX_VALUE_PAIRS(INSTANTIATE_VALUE_PAIR)
 
 }  // namespace amgx_hip

@@ -369,14 +369,8 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
     return (long long)h_nnz;
 }
 
-#define INSTANTIATE_SPGEMM_HASH(T)                                            \
-    template long long spgemm_hash<T>(const int*, const int*, const T*, int, \
-                                      const int*, const int*, const T*,      \
-                                      const int*, int, int, int*, int*, T*,  \
-                                      long long, int**, int*, hipStream_t);
-
-INSTANTIATE_SPGEMM_HASH(double)
-INSTANTIATE_SPGEMM_HASH(float)
+#define INSTANTIATE_SPGEMM_HASH(T) AMGX_INSTANTIATE(spgemm_hash, T)
+AMGX_REAL_TYPES(INSTANTIATE_SPGEMM_HASH)
 
 void free_device_buf(void* p, hipStream_t s) {
     HIP_CHECK(hipFreeAsync(p, s));

@@ -95,33 +95,39 @@ def _coef(v, alpha):
     return complex(alpha) if v.is_complex() else float(alpha)
 
 
+# op codes of _core.reduce_op: sum conj(x) y; sum|x|; max|x|; sum|x|^2
+# (complex x only)
+_RED_DOT, _RED_L1, _RED_LMAX, _RED_ABS2 = range(4)
+
+
 def dot(x, y):
-    r = _core.reduce_op(x.reshape(-1), y.reshape(-1), 0).item()
+    r = _core.reduce_op(x.reshape(-1), y.reshape(-1), _RED_DOT).item()
     # complex: conj(x) . y, the convention of ops/cpu.py (torch.vdot)
     return complex(r) if x.is_complex() else float(r)
 
 
 def nrm2(x):
     if x.is_complex():
-        # real accumulation of re^2 + im^2 (op 3), not Re(vdot(x, x))
-        return math.sqrt(float(_core.reduce_op(x.reshape(-1), None, 3).item()))
+        # real accumulation of re^2 + im^2, not Re(vdot(x, x))
+        return math.sqrt(float(_core.reduce_op(x.reshape(-1), None,
+                                               _RED_ABS2).item()))
     return math.sqrt(max(float(_core.reduce_op(x.reshape(-1), x.reshape(-1),
-                                               0).item()), 0.0))
+                                               _RED_DOT).item()), 0.0))
 
 
 def nrm1(x):
-    return float(_core.reduce_op(x.reshape(-1), None, 1).item())
+    return float(_core.reduce_op(x.reshape(-1), None, _RED_L1).item())
 
 
 def nrmmax(x):
-    return float(_core.reduce_op(x.reshape(-1), None, 2).item())
+    return float(_core.reduce_op(x.reshape(-1), None, _RED_LMAX).item())
 
 
 def dot_async(x, y):
     """Device-scalar dot (no host sync) for fused/graph paths; real only."""
     if x.is_complex():
         raise TypeError("dot_async is real-only (complex modes use dot)")
-    return _core.reduce_op(x.reshape(-1), y.reshape(-1), 0)
+    return _core.reduce_op(x.reshape(-1), y.reshape(-1), _RED_DOT)
 
 
 def axpy_dalpha(y, x, alpha, scale=1.0):

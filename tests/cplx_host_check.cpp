@@ -1,6 +1,7 @@
 // Stand-alone host check of amgx_amd/csrc/cplx.h (built and run by
 // tests/test_cplx_host.py): every operator of cplx<R> against std::complex<R>
-// on a fixed table of values, for R = double and float. Exit status 0 = pass.
+// on a fixed table of values, for R = double and float, and the real overloads
+// of conj_mul / abs / abs2 against the plain expressions. Exit status 0 = pass.
 //
 // Bound: each operator is a handful of correctly rounded operations, so a
 // result may differ from std::complex by a few ulp of the operand magnitudes
@@ -10,9 +11,11 @@
 // natural scale of the result is the tolerance; a wrong sign or a swapped
 // component misses it by a factor of 1/eps.
 
+#include <cmath>
 #include <complex>
 #include <cstdio>
 #include <limits>
+#include <type_traits>
 
 #include "cplx.h"
 
@@ -89,6 +92,31 @@ static void check_type(const char* name) {
             CHECK((a != b) == (sa != sb));
         }
     }
+    // real overloads (one reduction kernel serves real and complex T): one
+    // correctly rounded operation each, so they are exact against the plain
+    // expression, and they agree with the complex ones on a real argument
+    using amgx_hip::abs;
+    using amgx_hip::abs2;
+    using amgx_hip::conj_mul;
+    for (int i = 0; i < n; ++i) {
+        const R a = tab[i][0], im = tab[i][1];
+        CHECK(abs(a) == std::fabs(a) && abs(-a) == abs(a) && abs(a) >= R(0));
+        CHECK(abs2(a) == a * a && abs2(-a) == abs2(a));
+        CHECK(abs(C(a)) == abs(a) && abs2(C(a)) == abs2(a));
+        CHECK(conj_mul(a, im) == a * im && conj_mul(im, a) == a * im);
+        CHECK(conj_mul(C(a), C(im)).re == conj_mul(a, im));
+        CHECK(conj_mul(C(a), C(im)).im == R(0));
+        CHECK(conj_mul(a, a) == abs2(a));
+    }
+    static_assert(std::is_same<decltype(abs(R(1))), R>::value &&
+                  std::is_same<decltype(abs2(R(1))), R>::value &&
+                  std::is_same<decltype(conj_mul(R(1), R(1))), R>::value,
+                  "real overloads stay in the argument's precision");
+    static_assert(!amgx_hip::is_cplx<R>::value && amgx_hip::is_cplx<C>::value &&
+                  std::is_same<typename amgx_hip::real_of<R>::type, R>::value &&
+                  std::is_same<typename amgx_hip::real_of<C>::type, R>::value,
+                  "type traits of the reduction partials");
+
     // construction from a real: the kernels' TV(0) and T(1)
     CHECK(C(0).re == R(0) && C(0).im == R(0));
     CHECK(C(1).re == R(1) && C(1).im == R(0));

@@ -123,6 +123,66 @@ def test_residual_and_reductions():
     assert np.isclose(ops.dot(r, r), ops.dot(r_ref, r_ref), rtol=1e-12)
 
 
+RED_N = [1, 63, 257, 300001]    # the last one > NPART * 256 = 262144: the
+                                # grid-stride loop takes a second trip
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32],
+                         ids=["fp64", "fp32"])
+@pytest.mark.parametrize("n", RED_N)
+def test_real_reductions(n, dtype):
+    """dot / nrm2 / nrm1 / nrmmax on signed data against the host backend in
+    fp64 on the same (rounded) inputs. Bound, as derived at red_bound in
+    test_gpu_complex.py: the reduction adds at most 2 elements per thread and
+    then 18 tree levels, about 20 roundings of at most eps * sum|terms| each,
+    so 32 eps * sum|terms|; the square root halves the relative error of
+    nrm2, so 32 eps * nrm2 bounds it as well."""
+    from amgx_amd.ops import cpu as cpu_ops, gpu as gpu_ops
+    g = torch.Generator().manual_seed(1000 + n)
+    x = torch.randn(n, generator=g, dtype=torch.float64).to(dtype)
+    y = torch.randn(n, generator=g, dtype=torch.float64).to(dtype)
+    x64, y64 = x.double(), y.double()
+    xg, yg = x.cuda(), y.cuda()
+    eps = float(torch.finfo(dtype).eps)
+
+    want = {"dot": cpu_ops.dot(x64, y64), "nrm2": cpu_ops.nrm2(x64),
+            "nrm1": cpu_ops.nrm1(x64), "nrmmax": cpu_ops.nrmmax(x64)}
+    bound = {"dot": 32 * eps * float((x64.abs() * y64.abs()).sum()),
+             "nrm2": 32 * eps * want["nrm2"],
+             "nrm1": 32 * eps * want["nrm1"],
+             "nrmmax": 0.0}
+
+    def run():
+        return {"dot": ops.dot(xg, yg), "nrm2": ops.nrm2(xg),
+                "nrm1": ops.nrm1(xg), "nrmmax": ops.nrmmax(xg)}
+
+    got = run()
+    for name, val in got.items():
+        print(f"{name} n={n} {dtype}: got {val!r} want {want[name]!r} "
+              f"err {abs(val - want[name]):.3e} bound {bound[name]:.3e}")
+        assert isinstance(val, float)
+        assert abs(val - want[name]) <= bound[name], (name, val, want[name])
+    assert got == run()                     # bitwise reproducible
+
+    d = gpu_ops.dot_async(xg, yg)
+    assert d.is_cuda and d.shape == (1,) and d.dtype == dtype
+    assert float(d.item()) == got["dot"]
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32,
+                                   torch.complex128, torch.complex64],
+                         ids=["fp64", "fp32", "Z", "C"])
+def test_reduce_op_rejects_unknown_ops_and_lengths(dtype):
+    from amgx_amd import _core
+    x = torch.ones(100, dtype=dtype, device="cuda:0")
+    # op 3 (sum|x|^2) exists for complex x only; op 4 for nobody
+    for op in ((4,) if dtype.is_complex else (3, 4)):
+        with pytest.raises(RuntimeError, match="unknown op"):
+            _core.reduce_op(x, None, op)
+    with pytest.raises(RuntimeError, match="differ in length"):
+        _core.reduce_op(x, x[:99], 0)
+
+
 def test_blas1():
     x = torch.rand(10000, dtype=torch.float64)
     y = torch.rand(10000, dtype=torch.float64)

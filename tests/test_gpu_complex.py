@@ -221,7 +221,7 @@ def test_reduce_op_result_dtypes():
     from amgx_amd.ops import gpu as gpu_ops
     for dtype, real in ((Z, torch.float64), (C, torch.float32)):
         x = cvec(100, 12).to(dtype).to(DEV)
-        for op, want in ((0, dtype), (1, real), (2, real)):
+        for op, want in ((0, dtype), (1, real), (2, real), (3, real)):
             out = _core.reduce_op(x, x if op == 0 else None, op)
             assert out.dtype == want and out.shape == (1,)
         with pytest.raises(TypeError):
