@@ -49,6 +49,7 @@ class AMGHierarchy:
         t0 = time.perf_counter()
         self.levels = []
         dist = getattr(A, "manager", None)
+        self._check_complex(A)
         A = self._permute_fine(A)
         level = create_level(self.algorithm, A, self.scope, 0)
         self.levels.append(level)
@@ -83,11 +84,38 @@ class AMGHierarchy:
         if self.print_grid_stats and self.res.rank == 0:
             amgx_output(self.grid_stats() + "\n")
 
+    def _check_complex(self, A):
+        """Complex modes (?ZZI / ?CCI / ?ZCI) run aggregation AMG on scalar
+        matrices with V, W and F cycles; everything else raises here, before
+        any real-valued code path can drop an imaginary part."""
+        if not A.values.is_complex():
+            return
+
+        def no(what):
+            raise NotImplementedError(
+                f"{what} is not available in the complex modes")
+        if A.block_dim != 1:
+            no("AMG on a complex block matrix")
+        if self.algorithm != "AGGREGATION":
+            no(f"algorithm={self.algorithm} (classical / energymin AMG)")
+        if self.cycle_type in ("CG", "CGF"):
+            # the K-cycle recurrence (gamma * gamma / rho1) is the
+            # real-symmetric one
+            no(f"cycle={self.cycle_type} (the K-cycle)")
+        if getattr(A, "manager", None) is not None:
+            no("distributed AMG")
+        if int(self.scope.get("error_scaling") or 0) in (2, 3):
+            no("error_scaling 2 / 3")
+
     def resetup(self, A, reuse_levels: int):
         """Values-only re-setup: keep the coarsening structure (aggregates /
         C-F splits) of the first ``reuse_levels`` levels (<0 = all) and
         rebuild only Galerkin values, smoother factors and the coarse solver
         (reference structure_reuse_levels)."""
+        if A.values.is_complex():
+            raise NotImplementedError(
+                "structure-reuse resetup (structure_reuse_levels) is not "
+                "available in the complex modes")
         t0 = time.perf_counter()
         if reuse_levels < 0:
             reuse_levels = len(self.levels)

@@ -255,6 +255,9 @@ class AggregationLevel(AMGLevel):
         0.3 <= |lambda| <= 10 and cached for reuse_scale iterations."""
         import math
 
+        if self.A.values.is_complex():
+            raise NotImplementedError(
+                "error_scaling 2 / 3 is not available in the complex modes")
         if self._scale_counter > 0 and self._scale is not None:
             ef = torch.zeros_like(x)
             ops.prolongate_agg(ef, xc, self.aggregates, self.A.block_dim)
@@ -481,6 +484,10 @@ class EnergyminLevel(ClassicalLevel):
 
 
 def create_level(algorithm: str, A, scope, index) -> AMGLevel:
+    if A.values.is_complex() and algorithm != "AGGREGATION":
+        raise NotImplementedError(
+            f"algorithm={algorithm} (classical / energymin AMG) is not "
+            "available in the complex modes")
     if algorithm == "AGGREGATION":
         return AggregationLevel(A, scope, index)
     if algorithm == "CLASSICAL":

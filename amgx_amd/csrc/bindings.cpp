@@ -96,6 +96,13 @@ struct list_entry { using a = TA; using v = TV; };
                     c10::Join(" x ", _key));                                 \
     }()
 
+// the block kernels are real: a complex matrix is scalar CSR
+inline void check_scalar_if_complex(const Tensor& va, int64_t b,
+                                    const char* name) {
+    TORCH_CHECK(b == 1 || !va.is_complex(), name,
+                ": complex block matrices are unsupported");
+}
+
 // f(c, s, e) for every non-empty color c = slots [s, e) of rows_sorted, in
 // ascending or descending color order
 template <typename F>
@@ -192,7 +199,8 @@ void axpy(Tensor y, Tensor x, cscalar a) {
 // LDS-hash SpGEMM / Galerkin (kernels_spgemm.hip).  Returns
 // (roC, ciC, vaC, big_rows): big_rows lists rows written unsorted (the
 // Python caller sorts those).  Empty ciC + roC[-1]==-1 signals "fall back
-// to the ESC path" (a row exceeded the big hash capacity).
+// to the ESC path" (a row exceeded the top hash capacity of its value type,
+// SPGEMM_HASH_TOP_CAP).
 std::vector<Tensor> spgemm_hash(Tensor roA, Tensor ciA, Tensor vaA,
                                 Tensor roB, Tensor ciB, Tensor vaB,
                                 c10::optional<Tensor> aggcol, int64_t mode,
@@ -204,7 +212,7 @@ std::vector<Tensor> spgemm_hash(Tensor roA, Tensor ciA, Tensor vaA,
     auto big = torch::empty({0}, roA.options());
     hipStream_t st = cur_stream();
     long long nnz = -1;
-    DISPATCH(AMGX_REAL_TYPES, "spgemm_hash", (vaA), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "spgemm_hash", (vaA), [&] {
         int* big_rows = nullptr;
         int n_big = 0;
         nnz = amgx_hip::spgemm_hash<scalar_t>(
@@ -325,7 +333,8 @@ void jacobi_smooth(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
 void gs_smooth_rows(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                     Tensor bvec, Tensor x, Tensor rows, double omega) {
     int n = (int)(ro.numel() - 1);
-    DISPATCH(AMGX_REAL_PAIRS, "gs_smooth_rows", (va, x), [&] {
+    check_scalar_if_complex(va, b, "gs_smooth_rows");
+    DISPATCH(AMGX_VALUE_PAIRS, "gs_smooth_rows", (va, x), [&] {
         amgx_hip::gs_smooth_rows<scalar_a, scalar_v>(
             iptr(ro), iptr(ci), dptr<scalar_a>(va), dptr<scalar_a>(dinv),
             dptr<scalar_v>(bvec), dptr<scalar_v>(x), iptr(rows),
@@ -338,7 +347,8 @@ void gs_sweep(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
               Tensor bvec, Tensor x, Tensor rows_sorted,
               std::vector<int64_t> bounds, double omega, bool symmetric) {
     int n = (int)(ro.numel() - 1);
-    DISPATCH(AMGX_REAL_PAIRS, "gs_sweep", (va, x), [&] {
+    check_scalar_if_complex(va, b, "gs_sweep");
+    DISPATCH(AMGX_VALUE_PAIRS, "gs_sweep", (va, x), [&] {
         auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_smooth_rows<scalar_a, scalar_v>(
                 iptr(ro), iptr(ci), dptr<scalar_a>(va), dptr<scalar_a>(dinv),
@@ -358,7 +368,7 @@ void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
     int nc = (int)bounds.size() - 1;
     int64_t n = (int64_t)ro_s.numel() - 1;
     if (n <= amgx_hip::SMALL_LEVEL_ROWS) {
-        DISPATCH(AMGX_REAL_PAIRS, "gs_sweep_small", (va_s, x), [&] {
+        DISPATCH(AMGX_VALUE_PAIRS, "gs_sweep_small", (va_s, x), [&] {
             amgx_hip::gs_sweep_small<scalar_a, scalar_v>(
                 iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
                 dptr<scalar_a>(dinv_s), dptr<scalar_v>(bvec),
@@ -367,7 +377,7 @@ void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
         });
         return;
     }
-    DISPATCH(AMGX_REAL_PAIRS, "gs_sweep_sorted", (va_s, x), [&] {
+    DISPATCH(AMGX_VALUE_PAIRS, "gs_sweep_sorted", (va_s, x), [&] {
         auto run = [&](int, int64_t s, int64_t e) {
             amgx_hip::gs_rows_sorted<scalar_a, scalar_v>(
                 iptr(ro_s) + s, iptr(ci_s), dptr<scalar_a>(va_s),
@@ -385,9 +395,10 @@ Tensor dilu_setup(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor didx,
                   Tensor tidx, Tensor colors, Tensor rows_sorted,
                   std::vector<int64_t> bounds) {
     int n = (int)(ro.numel() - 1);
+    check_scalar_if_complex(va, b, "dilu_setup");
     auto einv = b == 1 ? torch::zeros({n}, va.options())
                        : torch::zeros({n, b, b}, va.options());
-    DISPATCH(AMGX_REAL_TYPES, "dilu_setup", (va), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "dilu_setup", (va), [&] {
         for_each_color(bounds, true, [&](int c, int64_t s, int64_t e) {
             amgx_hip::dilu_setup_color<scalar_t>(
                 iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(didx), iptr(tidx),
@@ -410,13 +421,14 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
                  Tensor w, Tensor z, Tensor x, double relax, bool fused) {
     TORCH_CHECK(!fused || b == 1 || b == 4,
                 "dilu_sorted: no fused-residual kernel for block_dim ", b);
+    check_scalar_if_complex(va_s, b, "dilu_sorted");
     int nc = (int)bounds.size() - 1;
     int bb = (int)(b * b);
     int64_t n = (int64_t)ro_s.numel() - 1;
     // small levels: ONE fused single-WG launch for the whole apply
     // (zeroing + all colors both sweeps + relaxed axpy)
     if (b == 1 && n <= amgx_hip::SMALL_LEVEL_ROWS) {
-        DISPATCH(AMGX_REAL_PAIRS, "dilu_small", (va_s, x), [&] {
+        DISPATCH(AMGX_VALUE_PAIRS, "dilu_small", (va_s, x), [&] {
             amgx_hip::dilu_small<scalar_a, scalar_v>(
                 iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
                 dptr<scalar_a>(einv_s), iptr(rows_sorted), iptr(bounds_dev),
@@ -428,7 +440,7 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
     }
     w.zero_();
     z.zero_();
-    DISPATCH(AMGX_REAL_PAIRS, "dilu_sorted", (va_s, x), [&] {
+    DISPATCH(AMGX_VALUE_PAIRS, "dilu_sorted", (va_s, x), [&] {
         hipStream_t st = cur_stream();
         const scalar_v* xres = fused ? dptr<scalar_v>(x) : nullptr;
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
@@ -487,7 +499,7 @@ Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
     auto prop = torch::empty({n}, ro.options().dtype(torch::kInt32));
     auto changed = torch::zeros({1}, ro.options().dtype(torch::kInt32));
     hipStream_t st = cur_stream();
-    DISPATCH(AMGX_REAL_TYPES, "size2_match", (va), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "size2_match", (va), [&] {
         for (int it = 0; it < max_iters; ++it) {
             amgx_hip::agg_propose<scalar_t>(
                 iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
@@ -510,7 +522,7 @@ Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
 // ---------------------------------------------------------------- transfers
 void restrict_agg(Tensor r, Tensor agg, int64_t b, Tensor rc) {
     rc.zero_();
-    DISPATCH(AMGX_REAL_TYPES, "restrict_agg", (r), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "restrict_agg", (r), [&] {
         amgx_hip::restrict_agg<scalar_t>(dptr<scalar_t>(r), iptr(agg),
                                          (int)agg.numel(), (int)b,
                                          dptr<scalar_t>(rc), cur_stream());
@@ -518,7 +530,7 @@ void restrict_agg(Tensor r, Tensor agg, int64_t b, Tensor rc) {
 }
 
 void restrict_csr(Tensor r, Tensor off, Tensor fids, int64_t b, Tensor rc) {
-    DISPATCH(AMGX_REAL_TYPES, "restrict_csr", (r), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "restrict_csr", (r), [&] {
         amgx_hip::restrict_csr<scalar_t>(
             iptr(off), iptr(fids), dptr<scalar_t>(r), (int)(off.numel() - 1),
             (int)b, dptr<scalar_t>(rc), cur_stream());
@@ -526,7 +538,7 @@ void restrict_csr(Tensor r, Tensor off, Tensor fids, int64_t b, Tensor rc) {
 }
 
 void prolongate_agg(Tensor x, Tensor xc, Tensor agg, int64_t b) {
-    DISPATCH(AMGX_REAL_TYPES, "prolongate_agg", (x), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "prolongate_agg", (x), [&] {
         amgx_hip::prolongate_agg<scalar_t>(
             dptr<scalar_t>(x), dptr<scalar_t>(xc), iptr(agg), (int)agg.numel(),
             (int)b, cur_stream());
@@ -535,7 +547,7 @@ void prolongate_agg(Tensor x, Tensor xc, Tensor agg, int64_t b) {
 
 // ---------------------------------------------------------------- dense
 void dense_gemv(Tensor Ainv, Tensor b, Tensor x) {
-    DISPATCH(AMGX_REAL_PAIRS, "dense_gemv", (Ainv, b), [&] {
+    DISPATCH(AMGX_VALUE_PAIRS, "dense_gemv", (Ainv, b), [&] {
         amgx_hip::dense_gemv<scalar_a, scalar_v>(
             dptr<scalar_a>(Ainv), dptr<scalar_v>(b), dptr<scalar_v>(x),
             (int)b.numel(), cur_stream());
@@ -544,7 +556,7 @@ void dense_gemv(Tensor Ainv, Tensor b, Tensor x) {
 
 // ---------------------------------------------------------------- pack
 void gather(Tensor src, Tensor idx, int64_t b, Tensor dst) {
-    DISPATCH(AMGX_REAL_TYPES, "gather", (src), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "gather", (src), [&] {
         amgx_hip::gather<scalar_t>(dptr<scalar_t>(src), iptr(idx),
                                    (int)idx.numel(), (int)b,
                                    dptr<scalar_t>(dst), cur_stream());
@@ -560,13 +572,14 @@ std::tuple<Tensor, Tensor, Tensor> galerkin_agg(Tensor ro, Tensor ci,
     int n = (int)(ro.numel() - 1);
     long long nnz = ci.numel();
     int bb = (int)(block_dim * block_dim);
+    check_scalar_if_complex(va, block_dim, "galerkin_agg");
     auto ro_c = torch::empty({nc + 1}, ro.options());
     auto ci_c = torch::empty({nnz}, ro.options());
     auto va_c = block_dim == 1
                     ? torch::empty({nnz}, va.options())
                     : torch::empty({nnz, block_dim, block_dim}, va.options());
     long long nnz_c = 0;
-    DISPATCH(AMGX_REAL_TYPES, "galerkin_agg", (va), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "galerkin_agg", (va), [&] {
         nnz_c = amgx_hip::galerkin_agg<scalar_t>(
             iptr(ro), iptr(ci), dptr<scalar_t>(va), n, nnz, iptr(agg),
             iptr(agg_col), (int)nc, (long long)ncmod, iptr(ro_c), iptr(ci_c),
@@ -585,7 +598,7 @@ std::tuple<Tensor, Tensor, Tensor> spgemm(Tensor roA, Tensor ciA, Tensor vaA,
     auto ci_c = torch::empty({capacity}, roA.options());
     auto va_c = torch::empty({capacity}, vaA.options());
     long long nnz_c = 0;
-    DISPATCH(AMGX_REAL_TYPES, "spgemm", (vaA), [&] {
+    DISPATCH(AMGX_VALUE_TYPES, "spgemm", (vaA), [&] {
         nnz_c = amgx_hip::spgemm_esc<scalar_t>(
             iptr(roA), iptr(ciA), dptr<scalar_t>(vaA), m, ciA.numel(),
             iptr(roB), iptr(ciB), dptr<scalar_t>(vaB), k, (int)n_cols_B,
@@ -794,6 +807,15 @@ void ilu0_apply_sorted(Tensor ro_s, Tensor ci_s, Tensor lu_s, Tensor diag_s,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.attr("SMALL_LEVEL_ROWS") = amgx_hip::SMALL_LEVEL_ROWS;
+    // widest row (entries) the LDS-hash SpGEMM / Galerkin takes, by value
+    // dtype; spgemm_hash signals the sort fallback for a wider one
+    m.attr("SPGEMM_HASH_TOP_CAP") = pybind11::dict(
+        pybind11::arg("float64") = amgx_hip::spgemm_hash_top_cap<double>(),
+        pybind11::arg("float32") = amgx_hip::spgemm_hash_top_cap<float>(),
+        pybind11::arg("complex128") =
+            amgx_hip::spgemm_hash_top_cap<cplx<double>>(),
+        pybind11::arg("complex64") =
+            amgx_hip::spgemm_hash_top_cap<cplx<float>>());
     m.def("csrmv", &csrmv);
     m.def("reduce_op", &reduce_op);
     m.def("axpy", &axpy);

@@ -33,7 +33,9 @@ namespace amgx_hip {
 
 // ============================================================ kernels_solve.hip
 // Launchers marked [value] are instantiated over the value types or value
-// pairs (real and complex); all others over the real lists only.
+// pairs (real and complex); all others over the real lists only. A [value]
+// launcher with a block size argument runs complex types for b == 1 only
+// and throws otherwise: the block kernels are real.
 
 // ---- SpMV family -----------------------------------------------------------
 // Mixed precision: TA = matrix-value type, TV = vector type. [value]
@@ -100,7 +102,8 @@ template <typename TA, typename TV>
 void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
                    const TV* bvec, const TV* xi, TV* xo, TV omega, int n,
                    int b, hipStream_t s);
-// in-place GS update of rows[count]: x[r] += omega*dinv[r]*(b - A x)[r]
+// in-place GS update of rows[count]: x[r] += omega*dinv[r]*(b - A x)[r].
+// [value]
 template <typename TA, typename TV>
 void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
                     const TA* dinv, const TV* bvec, TV* x, const int* rows,
@@ -111,6 +114,7 @@ void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
 // contiguous slab. Levels of at most SMALL_LEVEL_ROWS rows run the whole
 // sweep in one single-workgroup launch (*_small); larger levels launch once
 // per color with ro_s/rows/dinv_s/einv_s pre-offset to the color base.
+// All [value]; Einv is held in the matrix type.
 constexpr int SMALL_LEVEL_ROWS = 1 << 14;
 
 template <typename TA, typename TV>
@@ -150,6 +154,7 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
                       hipStream_t s);
 
 // ---- transfer operators ----------------------------------------------------
+// [value]
 template <typename T>
 void restrict_agg(const T* r, const int* agg, int n, int b, T* rc,
                   hipStream_t s);
@@ -162,10 +167,12 @@ void prolongate_agg(T* x, const T* xc, const int* agg, int n, int b,
                     hipStream_t s);
 
 // ---- dense coarse solve ----------------------------------------------------
+// [value]
 template <typename TA, typename TV>
 void dense_gemv(const TA* Ainv, const TV* b, TV* x, int n, hipStream_t s);
 
-// ---- gather for halo pack --------------------------------------------------
+// ---- gather for halo pack and the color-sorted slab copies ------------------
+// [value]
 template <typename T>
 void gather(const T* src, const int* idx, int count, int b, T* dst,
             hipStream_t s);
@@ -206,6 +213,8 @@ void color_minmax_round(const int* ro, const int* ci, int n,
                         int seed, int mode, int* n_uncolored, hipStream_t s);
 
 // ---- aggregation -----------------------------------------------------------
+// agg_propose / agg_merge_singletons: [value]; the edge weight of a complex
+// entry is its modulus, taken in double
 template <typename T>
 void agg_propose(const int* ro, const int* ci, const T* va, const int* tidx,
                  const T* diag, int n, const int* agg, int* prop, int seed,
@@ -224,7 +233,7 @@ void agg_merge_singletons(const int* ro, const int* ci, const T* va,
 // agg = per-ROW local coarse id (n entries); agg_col = per-COLUMN coarse id
 // (n_cols entries; equals agg for single-process, GLOBAL coarse ids for the
 // distributed path); nc = local coarse rows (ro_c size); ncmod = column-id
-// modulus (global coarse columns).
+// modulus (global coarse columns). [value], complex for bb == 1 only.
 template <typename T>
 long long galerkin_agg(const int* ro, const int* ci, const T* va, int n,
                        long long nnz, const int* agg, const int* agg_col,
@@ -234,7 +243,7 @@ long long galerkin_agg(const int* ro, const int* ci, const T* va, int n,
 // General ESC SpGEMM: C = A(m x k) @ B(k x n). Outputs sized by caller at
 // the expansion worst case is impractical; instead ci_c/va_c must be sized
 // >= nnz(C); pass capacity = expansion bound from Python (sum deg). Returns
-// nnz_c. Temps allocated internally.
+// nnz_c. Temps allocated internally. [value]
 template <typename T>
 long long spgemm_esc(const int* roA, const int* ciA, const T* vaA, int m,
                      long long nnzA, const int* roB, const int* ciB,
@@ -251,8 +260,14 @@ void transpose_csr(const int* ro, const int* ci, const T* va, int m, int n,
 // LDS-hash SpGEMM
 // mode 0: C = A*B.  mode 1: aggregation Galerkin — A = aggregate-membership
 // CSR (coarse row -> fine rows), B = fine matrix, key = aggcol[col].
-// Returns nnz(C), or -1 when a row exceeds the big-table capacity (caller
+// Returns nnz(C), or -1 when a row exceeds the top-tier capacity of T (caller
 // falls back to the ESC sort path), or -2 when cap_nnz is too small.
+// Instantiated over the value types.
+// The top tier is one wave per workgroup with one key + one value array in
+// LDS: 8192 entries for values of up to 8 bytes (96 KB), 4096 for
+// cplx<double> (80 KB; 8192 x 20 B would take all 160 KB of a CU).
+template <typename T>
+constexpr int spgemm_hash_top_cap() { return sizeof(T) > 8 ? 4096 : 8192; }
 // big_rows_out (device, caller frees via free_device_buf) lists rows whose
 // entries were written UNSORTED (caller sorts those columns).
 template <typename T>

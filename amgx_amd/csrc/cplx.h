@@ -105,6 +105,18 @@ AMGX_HD float abs(float a) { return std::fabs(a); }
 AMGX_HD double abs2(double a) { return a * a; }
 AMGX_HD float abs2(float a) { return a * a; }
 
+// |a| in double whatever the storage type: the magnitude the setup kernels
+// compare (matching edge weights, the DILU pivot guard). Complex: the modulus
+// from the two parts widened to double first, so a complex64 entry whose
+// modulus is representable compares exactly like its real counterpart.
+AMGX_HD double absd(double a) { return std::fabs(a); }
+AMGX_HD double absd(float a) { return std::fabs((double)a); }
+template <typename R>
+AMGX_HD double absd(const cplx<R>& a) {
+    double re = (double)a.re, im = (double)a.im;
+    return std::sqrt(re * re + im * im);
+}
+
 template <typename T> struct is_cplx { static constexpr bool value = false; };
 template <typename R> struct is_cplx<cplx<R>> { static constexpr bool value = true; };
 // R for cplx<R>, T itself for a real T: the type of |x| and of a norm
@@ -128,6 +140,17 @@ __device__ __forceinline__ cplx<R> __shfl_xor(const cplx<R>& v, int mask,
                                               int width = warpSize) {
     return cplx<R>(::__shfl_xor(v.re, mask, width),
                    ::__shfl_xor(v.im, mask, width));
+}
+
+// Accumulation into a complex slot is one atomic per part (LDS hash tables,
+// the atomic restriction). The two parts of a slot are therefore only
+// consistent once every contributor is done: read them after the barrier or
+// kernel boundary that ends the accumulation, never in between.
+using ::atomicAdd;
+template <typename R>
+__device__ __forceinline__ void atomicAdd(cplx<R>* p, const cplx<R>& v) {
+    ::atomicAdd(&p->re, v.re);
+    ::atomicAdd(&p->im, v.im);
 }
 #endif
 

@@ -107,10 +107,11 @@ template <typename T>
 __device__ __forceinline__ double edge_weight(const T* va, const int* tidx,
                                               const T* diag, int k, int i,
                                               int j) {
-    double aij = fabs((double)va[k]);
-    double aji = tidx[k] >= 0 ? fabs((double)va[tidx[k]]) : 0.0;
-    double di = fabs((double)diag[i]);
-    double dj = fabs((double)diag[j]);
+    // absd: |.| in double, the modulus for complex values (cplx.h)
+    double aij = absd(va[k]);
+    double aji = tidx[k] >= 0 ? absd(va[tidx[k]]) : 0.0;
+    double di = absd(diag[i]);
+    double dj = absd(diag[j]);
     double scale = rsqrt((di > 0 ? di : 1.0) * (dj > 0 ? dj : 1.0));
     return (aij + aji) * scale;
 }
@@ -330,6 +331,9 @@ long long galerkin_agg(const int* ro, const int* ci, const T* va, int n,
     K* keys_alt = keys + nnz;
     long long nc_ll = ncmod;
 
+    if (is_cplx<T>::value && bb != 1)
+        throw std::runtime_error(
+            "galerkin_agg: complex block matrices are unsupported");
     if (bb == 1) {
         T* vals = (T*)dev_alloc(nnz * sizeof(T) * 2, s);
         T* vals_alt = vals + nnz;
@@ -592,13 +596,16 @@ void transpose_csr(const int* ro, const int* ci, const T* va, int m, int n,
 }
 
 // ============================================================ instantiation
+// aggregation setup (matching, Galerkin, ESC SpGEMM) over the value types;
+// the transpose serves classical AMG only and stays real
 #define INSTANTIATE_SETUP(T)                                                   \
     AMGX_INSTANTIATE(agg_propose, T)                                           \
     AMGX_INSTANTIATE(agg_merge_singletons, T)                                  \
     AMGX_INSTANTIATE(galerkin_agg, T)                                          \
-    AMGX_INSTANTIATE(spgemm_esc, T)                                            \
-    AMGX_INSTANTIATE(transpose_csr, T)
+    AMGX_INSTANTIATE(spgemm_esc, T)
+#define INSTANTIATE_SETUP_REAL(T) AMGX_INSTANTIATE(transpose_csr, T)
 
-AMGX_REAL_TYPES(INSTANTIATE_SETUP)
+AMGX_VALUE_TYPES(INSTANTIATE_SETUP)
+AMGX_REAL_TYPES(INSTANTIATE_SETUP_REAL)
 
 }  // namespace amgx_hip

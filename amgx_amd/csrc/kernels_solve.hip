@@ -656,6 +656,9 @@ void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
         hipLaunchKernelGGL((gs_rows_scalar<TA, TV>), dim3(grid_1d(count)),
                            dim3(AMGX_BLOCK), 0, s, ro, ci, va, dinv, bvec, x,
                            rows, count, omega);
+    } else if constexpr (is_cplx<TV>::value) {
+        throw std::runtime_error(
+            "gs_smooth_rows: complex block matrices are unsupported");
     } else {
         hipLaunchKernelGGL((gs_rows_block<TA, TV>), dim3(grid_1d(count)),
                            dim3(AMGX_BLOCK), 0, s, ro, ci, va, dinv, bvec, x,
@@ -688,7 +691,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_setup_scalar(const int* __res
     // tiny-pivot safeguard: a near-zero modified pivot cascades huge Einv
     // through later colors — fall back to the plain diagonal
     T dref = (d != T(0)) ? d : T(1);
-    if (fabs((double)e) < 1e-10 * fabs((double)dref)) e = dref;
+    if (absd(e) < 1e-10 * absd(dref)) e = dref;
     einv[i] = T(1) / e;
 }
 
@@ -758,6 +761,9 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
         hipLaunchKernelGGL((dilu_setup_scalar<T>), dim3(grid_1d(count)),
                            dim3(AMGX_BLOCK), 0, s, ro, ci, va, didx, tidx,
                            colors, rows, count, color, einv);
+    } else if constexpr (is_cplx<T>::value) {
+        throw std::runtime_error(
+            "dilu_setup: complex block matrices are unsupported");
     } else if (b == 4) {   // MFMA triple-product path (kernels_mfma.hip)
         dilu_setup_b4<T>(ro, ci, va, didx, tidx, colors, rows, count, color,
                          einv, s);
@@ -942,6 +948,9 @@ void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
         hipLaunchKernelGGL(kern, dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0,
                            s, ro_s, ci_s, va_s, einv_s, rows, count, rhs,
                            xres, w);
+    } else if constexpr (is_cplx<TV>::value) {
+        throw std::runtime_error(
+            "dilu_fwd_sorted: complex block matrices are unsupported");
     } else if (b == 4) {   // MFMA wave kernel (kernels_mfma.hip)
         dilu_fwd_b4_sorted<TA, TV>(ro_s, ci_s, va_s, einv_s, rows, count,
                                    rhs, xres, w, s);
@@ -957,17 +966,21 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s) {
     if (count <= 0) return;
-    if (b == 1)
+    if (b == 1) {
         hipLaunchKernelGGL((dilu_bwd_scalar_sorted<TA, TV>),
                            dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
                            ro_s, ci_s, va_s, einv_s, rows, count, wv, z);
-    else if (b == 4)       // MFMA wave kernel (kernels_mfma.hip)
+    } else if constexpr (is_cplx<TV>::value) {
+        throw std::runtime_error(
+            "dilu_bwd_sorted: complex block matrices are unsupported");
+    } else if (b == 4) {   // MFMA wave kernel (kernels_mfma.hip)
         dilu_bwd_b4_sorted<TA, TV>(ro_s, ci_s, va_s, einv_s, rows, count,
                                    wv, z, s);
-    else
+    } else {
         hipLaunchKernelGGL((dilu_bwd_block_sorted<TA, TV>),
                            dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
                            ro_s, ci_s, va_s, einv_s, rows, count, wv, z, b);
+    }
 }
 
 // ============================================================ transfers
@@ -1089,26 +1102,31 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
 }
 
 // ============================================================ instantiation
-// over the type lists of core_api.h; complex types get the Krylov + Jacobi
-// subset (scalar CSR), whose template bodies are the real ones
+// over the type lists of core_api.h; complex types get the scalar-CSR
+// kernels (Krylov, Jacobi, multicolor GS / DILU, transfers, dense GEMV),
+// whose template bodies are the real ones. Block kernels stay real: their
+// launchers compile the block branch out for complex types and throw.
 #define INSTANTIATE_REAL(T)                                                     \
     AMGX_INSTANTIATE(axpy_dalpha, T)                                            \
-    AMGX_INSTANTIATE(scal_drsqrt, T)                                            \
-    AMGX_INSTANTIATE(dilu_setup_color, T)                                       \
-    AMGX_INSTANTIATE(restrict_agg, T)                                           \
-    AMGX_INSTANTIATE(restrict_csr, T)                                           \
-    AMGX_INSTANTIATE(prolongate_agg, T)                                         \
-    AMGX_INSTANTIATE(gather, T)
+    AMGX_INSTANTIATE(scal_drsqrt, T)
 #define INSTANTIATE_VALUE(T)                                                    \
     AMGX_INSTANTIATE(reduce, T)                                                 \
     AMGX_INSTANTIATE(axpy, T)                                                   \
     AMGX_INSTANTIATE(axpby, T)                                                  \
     AMGX_INSTANTIATE(scal, T)                                                   \
     AMGX_INSTANTIATE(extract_diag, T)                                           \
-    AMGX_INSTANTIATE(jacobi_dinv, T)
+    AMGX_INSTANTIATE(jacobi_dinv, T)                                            \
+    AMGX_INSTANTIATE(dilu_setup_color, T)                                       \
+    AMGX_INSTANTIATE(restrict_agg, T)                                           \
+    AMGX_INSTANTIATE(restrict_csr, T)                                           \
+    AMGX_INSTANTIATE(prolongate_agg, T)                                         \
+    AMGX_INSTANTIATE(gather, T)
 #define INSTANTIATE_REAL_PAIR(TA, TV)                                           \
     AMGX_INSTANTIATE(bsrmv, TA, TV)                                             \
-    AMGX_INSTANTIATE(bsrmv_generic, TA, TV)                                     \
+    AMGX_INSTANTIATE(bsrmv_generic, TA, TV)
+#define INSTANTIATE_VALUE_PAIR(TA, TV)                                          \
+    AMGX_INSTANTIATE(csrmv, TA, TV)                                             \
+    AMGX_INSTANTIATE(jacobi_smooth, TA, TV)                                     \
     AMGX_INSTANTIATE(dilu_small, TA, TV)                                        \
     AMGX_INSTANTIATE(dilu_fwd_sorted, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_bwd_sorted, TA, TV)                                   \
@@ -1116,9 +1134,6 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
     AMGX_INSTANTIATE(gs_rows_sorted, TA, TV)                                    \
     AMGX_INSTANTIATE(gs_smooth_rows, TA, TV)                                    \
     AMGX_INSTANTIATE(dense_gemv, TA, TV)
-#define INSTANTIATE_VALUE_PAIR(TA, TV)                                          \
-    AMGX_INSTANTIATE(csrmv, TA, TV)                                             \
-    AMGX_INSTANTIATE(jacobi_smooth, TA, TV)
 
 AMGX_REAL_TYPES(INSTANTIATE_REAL)
 AMGX_VALUE_TYPES(INSTANTIATE_VALUE)

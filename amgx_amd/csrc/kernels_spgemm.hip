@@ -13,8 +13,9 @@
 //   fill pass:  wave-per-row LDS hash MAP (col -> accumulated value),
 //               compacted + bitonic-sorted in LDS, written coalesced
 // Rows overflowing the 4-wave/WG capacity run again in a 1-wave/WG kernel
-// with a 8-16x larger table (96-128 KB LDS); rows beyond THAT fall back to
-// the ESC sort path at the Python dispatch level (rare: >8k nnz per row).
+// with a 8-16x larger table (80-96 KB LDS); rows beyond THAT fall back to
+// the ESC sort path at the Python dispatch level (rare: >8k nnz per row,
+// >4k for complex128 values).
 
 #include <cstring>
 
@@ -32,7 +33,19 @@ namespace {
 constexpr int TINY_CAP = 64;       // per-wave table, 8 waves per WG —
                                    // right-sized for AMG rows (<=64 nnz)
 constexpr int SMALL_CAP = 512;     // per-wave table, 4 waves per WG
-constexpr int BIG_CAP = 8192;      // 1 wave per WG
+// top tier, 1 wave per WG: spgemm_hash_top_cap<T>() of core_api.h, 8192
+// entries (4096 for cplx<double>)
+
+// LDS bytes of one spgemm_fill_kernel workgroup: keys + values per wave, the
+// compaction copy of both in the sorted tiers (one dummy element each
+// otherwise) and the per-wave cursor
+constexpr int LDS_BYTES = 160 * 1024;       // per CU on gfx950
+template <typename T>
+constexpr long long fill_lds_bytes(int cap, int waves, bool sorted) {
+    long long entry = (long long)(sizeof(int) + sizeof(T));
+    return waves * (cap * entry + (sorted ? cap : 1) * entry
+                    + (long long)sizeof(int));
+}
 
 __device__ __forceinline__ unsigned int hash_col(int c) {
     unsigned int a = (unsigned int)c;
@@ -62,7 +75,9 @@ __device__ __forceinline__ int hset_insert(int* keys, int cap, int key) {
     return -1;
 }
 
-// hash-MAP accumulate (fill pass)
+// hash-MAP accumulate (fill pass). A complex value takes one LDS atomic per
+// part (cplx.h); the fill kernel reads a slot only after the wave barrier
+// that follows its accumulation loop.
 template <typename T>
 __device__ __forceinline__ bool hmap_add(int* keys, T* vals, int cap,
                                          int key, T v) {
@@ -166,6 +181,8 @@ __global__ __launch_bounds__(64 * WAVES) void spgemm_fill_kernel(
     const int* __restrict__ aggcol, int mode, int m,
     const int* __restrict__ row_list, int n_rows,
     const int* __restrict__ roC, int* __restrict__ ciC, T* __restrict__ vaC) {
+    static_assert(fill_lds_bytes<T>(CAP, WAVES, SORTED) <= LDS_BYTES,
+                  "spgemm_fill_kernel: hash tables exceed the LDS of a CU");
     __shared__ int keys_s[WAVES][CAP];
     __shared__ T vals_s[WAVES][CAP];
     __shared__ int ck_s[WAVES][SORTED ? CAP : 1];
@@ -232,16 +249,18 @@ __global__ __launch_bounds__(64 * WAVES) void spgemm_fill_kernel(
 }
 
 // ============================================================ driver
-// Returns nnz(C) >= 0 on success, -1 when a row exceeded BIG_CAP (caller
+// Returns nnz(C) >= 0 on success, -1 when a row exceeded the top tier (caller
 // falls back to the ESC sort path).  counts/roC share the (m+1) buffer.
-// cap0 chooses the first tier of the 64 -> 512 -> 8192 capacity ladder
-// (64 for AMG-shaped rows; rows past a tier re-run in the next).
+// cap0 chooses the first tier of the 64 -> 512 -> top capacity ladder
+// (64 for AMG-shaped rows; rows past a tier re-run in the next); the top
+// tier holds spgemm_hash_top_cap<T>() entries.
 template <typename T>
 long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
                       const int* roB, const int* ciB, const T* vaB,
                       const int* aggcol, int mode, int cap0, int* roC_out,
                       int* ciC_cap_buf, T* vaC_cap_buf, long long cap_nnz,
                       int** big_rows_out, int* n_big_out, hipStream_t s) {
+    constexpr int BIG_CAP = spgemm_hash_top_cap<T>();
     int* counts = nullptr;
     HIP_CHECK(hipMallocAsync(&counts, (m + 1) * sizeof(int), s));
     int* ovf = nullptr;
@@ -285,7 +304,7 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
     };
     int* mid_rows = nullptr;   // rows needing the 512 tier (only if tiny)
     int n_mid = 0;
-    int* big_rows = nullptr;   // rows needing the 8192 tier
+    int* big_rows = nullptr;   // rows needing the top tier
     int n_big = 0;
     if (h_ovf && tiny_first) {
         n_mid = collect_marked(&mid_rows);
@@ -370,7 +389,7 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
 }
 
 #define INSTANTIATE_SPGEMM_HASH(T) AMGX_INSTANTIATE(spgemm_hash, T)
-AMGX_REAL_TYPES(INSTANTIATE_SPGEMM_HASH)
+AMGX_VALUE_TYPES(INSTANTIATE_SPGEMM_HASH)
 
 void free_device_buf(void* p, hipStream_t s) {
     HIP_CHECK(hipFreeAsync(p, s));

@@ -17,6 +17,19 @@ def _np(x: torch.Tensor) -> np.ndarray:
     return x.detach().numpy()
 
 
+def _real_only(A, feature: str):
+    """Host paths that compute in float64 refuse complex matrices (hZZI /
+    hCCI / hZCI) instead of casting the imaginary part away."""
+    if A.values.is_complex():
+        raise NotImplementedError(
+            f"{feature} is not available in the complex modes")
+
+
+def _work_dtype(A):
+    """numpy accumulation dtype of the host kernels for A's values."""
+    return np.complex128 if A.values.is_complex() else np.float64
+
+
 def _csr(A) -> sp.csr_matrix:
     m = A.to_scipy()
     if not sp.issparse(m):
@@ -134,6 +147,7 @@ def jacobi_dinv(A, l1: bool = False) -> torch.Tensor:
             else torch.float64
         d = extract_diagonal(A).to(work_dtype).clone()
         if l1:
+            _real_only(A, "JACOBI_L1 (the l1 diagonal)")
             m = _csr(A)
             abssum = np.abs(m).sum(axis=1).A1 - np.abs(_np(extract_diagonal(A)))
             d += torch.from_numpy(np.sign(_np(d)) * abssum)
@@ -141,6 +155,7 @@ def jacobi_dinv(A, l1: bool = False) -> torch.Tensor:
         d = torch.where(d.abs() > 0, d, torch.ones_like(d))
         return (1.0 / d).to(A.dtype)
     # block
+    _real_only(A, "a block matrix (block Jacobi diagonal)")
     b = A.block_dim
     D = extract_diagonal(A).double().clone()  # (n, b, b)
     if l1:
@@ -280,6 +295,7 @@ def _strength_weights(A):
 def _block_norm_csr(A) -> sp.csr_matrix:
     """Frobenius norm of each block -> scalar CSR (for selectors/coloring on
     block matrices)."""
+    _real_only(A, "a block matrix (Frobenius block norms)")
     vals = _np(A.values)
     norms = np.sqrt((vals.astype(np.float64) ** 2).sum(axis=(1, 2)))
     # keep signs of diagonal-ish entries irrelevant; selectors use |.| anyway
@@ -465,6 +481,7 @@ def truncate_rows(P, trunc_factor: float = 0.0, max_elements: int = -1):
         trunc_factor = 0.0
     if trunc_factor <= 0.0 and max_elements < 0:
         return P
+    _real_only(P, "interpolation truncation")
     m = _csr(P).copy()
     n = m.shape[0]
     data, indices, indptr = m.data, m.indices, m.indptr
@@ -501,10 +518,21 @@ def dilu_setup(A, coloring):
         m = _csr(A)
         if m.shape[1] != m.shape[0]:
             m = m[:, :m.shape[0]].tocsr()  # distributed: local couplings only
-        d = m.diagonal().astype(np.float64)
-        # B_ij = a_ij * a_ji where both exist
+        wd = _work_dtype(A)
+        if A.values.is_complex():
+            # as on the device (ops/gpu.py:_check_dilu_coloring): coupled
+            # rows of one color make the factor and the sweeps meaningless
+            coo = m.tocoo()
+            clash = (coo.row != coo.col) & (colors[coo.row] == colors[coo.col])
+            if clash.any():
+                raise RuntimeError(
+                    "dilu_setup: the coloring is not a valid distance-1 "
+                    f"coloring of the matrix ({int(clash.sum())} couplings "
+                    "join rows of one color)")
+        d = m.diagonal().astype(wd)
+        # B_ij = a_ij * a_ji where both exist (plain transpose, no conjugate)
         B = m.multiply(m.T).tocsr()
-        einv = np.zeros(A.n_rows, dtype=np.float64)
+        einv = np.zeros(A.n_rows, dtype=wd)
         done = np.zeros(A.n_rows, dtype=np.float64)
         for c in range(coloring.num_colors):
             rows = np.nonzero(colors == c)[0]
@@ -519,6 +547,7 @@ def dilu_setup(A, coloring):
             done[rows] = 1.0
         return torch.from_numpy(einv).to(A.dtype)
     # block version (host reference, O(nnz*b^3) python loop on small tests)
+    _real_only(A, "a block matrix (block DILU)")
     ro = _np(A.row_offsets).astype(np.int64)
     ci = _np(A.col_indices).astype(np.int64)
     vals = _np(A.values).astype(np.float64)
@@ -570,9 +599,13 @@ def dilu_solve(A, Einv, coloring, r, relaxation, x):
     bd = A.block_dim
     colors = _np(coloring.colors).astype(np.int64)
     m = A.to_scipy()
-    rv = _np(r).reshape(-1).astype(np.float64)
+    if bd != 1:
+        _real_only(A, "a block matrix (block DILU)")
+    wd = np.complex128 if (A.values.is_complex() or r.is_complex()) \
+        else np.float64
+    rv = _np(r).reshape(-1).astype(wd)
     w = np.zeros_like(rv)
-    ei = _np(Einv).astype(np.float64)
+    ei = _np(Einv).astype(wd)
     nc = coloring.num_colors
     def rowsb(rows):
         return (rows[:, None] * bd + np.arange(bd)[None, :]).reshape(-1)
@@ -607,8 +640,9 @@ def dilu_solve(A, Einv, coloring, r, relaxation, x):
 
 # ---------------------------------------------------------------------- dense
 def dense_solve(Ainv, b, x):
-    x.reshape(-1).copy_(
-        (Ainv.to(torch.float64) @ b.reshape(-1).to(torch.float64)).to(x.dtype))
+    wd = torch.complex128 if (Ainv.is_complex() or b.is_complex()) \
+        else torch.float64
+    x.reshape(-1).copy_((Ainv.to(wd) @ b.reshape(-1).to(wd)).to(x.dtype))
     return x
 
 
@@ -618,6 +652,7 @@ def ilu0_setup(A, coloring):
     factored values aligned with A's CSR structure. Host reference for the
     per-color GPU kernels (reference src/solvers/multicolor_ilu_solver.cu;
     block path: its setup_LU bxb kernels).""" 
+    _real_only(A, "MULTICOLOR_ILU")
     if A.block_dim != 1:
         return _ilu0_setup_block(A, coloring)
     ro = _np(A.row_offsets).astype(np.int64)
@@ -730,6 +765,7 @@ def _ilu0_solve_block(A, factors, coloring, r, x, relaxation=1.0):
 
 
 def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):
+    _real_only(A, "MULTICOLOR_ILU")
     if A.block_dim != 1:
         return _ilu0_solve_block(A, factors, coloring, r, x, relaxation)
     ro = _np(A.row_offsets).astype(np.int64)
@@ -770,6 +806,7 @@ def strength_ahat(A, theta: float = 0.25, max_row_sum: float = 1.1):
     |a_ij| >= theta * max_{k!=i}|a_ik| (reference
     src/classical/strength/strength_base.cu; SURVEY.md 'classic |a_ij|>=th*max').
     Rows whose |row sum| exceeds max_row_sum*|a_ii| are made all-weak."""
+    _real_only(A, "classical AMG (AHAT strength)")
     ro = _np(A.row_offsets).astype(np.int64)
     ci = _np(A.col_indices).astype(np.int64)
     v = _np(A.values).astype(np.float64)
@@ -847,6 +884,7 @@ def interp_d1(A, S, cf_map, num_coarse):
     formula has no cross-row coupling), so host-mode and the distributed
     classical setup scale to multi-million-row partitions."""
     from ..matrix import CSRMatrix
+    _real_only(A, "classical AMG (distance-1 interpolation)")
     ro = _np(A.row_offsets).astype(np.int64)
     ci = _np(A.col_indices).astype(np.int64)
     v = _np(A.values).astype(np.float64)

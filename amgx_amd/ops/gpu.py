@@ -279,7 +279,30 @@ class DiluState:
         return self.einv.cpu()
 
 
+def _check_dilu_coloring(A, coloring):
+    """DILU reads Einv_j and w_j of every coupled row j of an earlier color
+    and takes same-color rows as uncoupled; two coupled rows of one color
+    would be skipped by the factor and raced on by the sweeps. The complex
+    modes check this once per setup; the real modes keep their setup as it
+    was and rely on the coloring they are given."""
+    n = A.n_rows
+    ro = A.row_offsets.to(torch.int64)
+    rows = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.int64, device=A.device), ro[1:] - ro[:-1])
+    cols = A.col_indices.to(torch.int64)
+    off = (cols != rows) & (cols < n)
+    colors = coloring.colors.to(torch.int64)
+    clash = off & (colors[rows] == colors[cols.clamp(max=n - 1)])
+    if bool(clash.any()):
+        raise RuntimeError(
+            "dilu_setup: the coloring is not a valid distance-1 coloring of "
+            f"the matrix ({int(clash.sum())} couplings join rows of one "
+            "color)")
+
+
 def dilu_setup(A, coloring):
+    if A.values.is_complex():
+        _check_dilu_coloring(A, coloring)
     einv = _core.dilu_setup(A.row_offsets, A.col_indices, A.values,
                             A.block_dim, _didx(A), _tidx(A), coloring.colors,
                             coloring.rows_sorted, coloring.bounds)
@@ -323,9 +346,13 @@ def dilu_solve(A, Einv, coloring, r, relaxation, x):
 # ---------------------------------------------------------------------- aggregation
 def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
                    seed: int = 0):
+    if A.block_dim > 1 and A.values.is_complex():
+        raise NotImplementedError(
+            "aggregation of a block matrix is not available in the complex "
+            "modes (dZZI / dCCI / dZCI)")
     diag = extract_diagonal(A)
     if A.block_dim > 1:
-        # Frobenius norms drive the matching for block matrices
+        # Frobenius norms drive the matching for real block matrices
         diag = torch.linalg.vector_norm(diag.reshape(A.n_rows, -1), dim=1)
         va = torch.linalg.vector_norm(
             A.values.reshape(A.nnz, -1).to(torch.float64), dim=1).to(A.dtype)
@@ -333,6 +360,8 @@ def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
                                   diag.to(A.dtype), A.n_rows, max_iterations,
                                   int(seed) + 0x9E3779B1)
     else:
+        # scalar, real or complex: the kernel weighs an edge by |a_ij|,
+        # the modulus for complex values
         roots = _core.size2_match(A.row_offsets, A.col_indices, A.values,
                                   _tidx(A), diag, A.n_rows, max_iterations,
                                   int(seed) + 0x9E3779B1)
@@ -345,6 +374,11 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
     """agg_col/ncols_mod: distributed variant — per-column coarse ids (GLOBAL)
     and the global coarse column count; defaults to the single-process case.
 
+    Real and complex values alike (complex: scalar matrices only). A
+    row wider than the top hash tier of the value type
+    (_core.SPGEMM_HASH_TOP_CAP: 8192 entries, 4096 for complex128) takes the
+    one-sort generator.
+
     Scalar matrices run the LDS-hash LOW_DEG-style generator
     (kernels_spgemm.hip mode 1: wave-per-coarse-row hash accumulation —
     reference src/aggregation/coarseAgenerators/low_deg_…); block matrices,
@@ -355,6 +389,10 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
         agg_col = aggregates
     if ncols_mod is None:
         ncols_mod = num_aggregates
+    if A.block_dim > 1 and A.values.is_complex():
+        raise NotImplementedError(
+            "the Galerkin product of a block matrix is not available in the "
+            "complex modes (dZZI / dCCI / dZCI)")
     if A.block_dim == 1 and generator != "THRUST":
         # aggregate-membership CSR: coarse row -> fine member rows
         agg64 = aggregates.to(torch.int64)
@@ -406,7 +444,7 @@ def _expansion_bound(A, B):
 
 
 def _sort_unsorted_rows(ro, ci, va, big_rows):
-    """Column-sort the (rare) rows the big-capacity hash kernel wrote
+    """Column-sort the (rare) rows the top-tier hash kernel wrote
     unsorted (>512 nnz per row)."""
     ro64 = ro.to(torch.int64)
     for r in big_rows.tolist():
@@ -419,7 +457,8 @@ def _sort_unsorted_rows(ro, ci, va, big_rows):
 def spgemm(A, B):
     """C = A*B — LDS-hash kernels (kernels_spgemm.hip, role of reference
     src/csr_multiply_detail.cu warp-hash family); ESC sort fallback for
-    pathological >8k-nnz rows."""
+    pathological rows past the top hash tier (>8k nnz, >4k for
+    complex128)."""
     from ..matrix import CSRMatrix
     cap = max(_expansion_bound(A, B), 1)
     # first hash tier sized to the average output row (AMG rows are tiny)

@@ -20,6 +20,9 @@ from .base import Solver, register_solver
 
 register_parameter("use_hip_graph", int, 1,
                    "capture the AMG cycle into a hipGraph (device path)")
+register_parameter("hipgraph_cycle", int, 0,
+                   "1 = request the hipGraph cycle explicitly (as "
+                   "use_hip_graph=1 does)")
 
 
 @register_solver("AMG")
@@ -28,12 +31,25 @@ class AMGSolver(Solver):
 
     def __init__(self, scope, resources):
         super().__init__(scope, resources)
-        self.use_graph = bool(scope.get("use_hip_graph"))
+        self.use_graph = bool(scope.get("use_hip_graph")) \
+            or bool(scope.get("hipgraph_cycle"))
+        # asked for by the configuration, not merely on by default
+        self._graph_requested = bool(scope.get("hipgraph_cycle")) or (
+            scope.has("use_hip_graph") and bool(scope.get("use_hip_graph")))
         self._graph = None
         self._graph_failed = False
 
     def solver_setup(self):
         from ..amg.amg import AMGHierarchy
+        if self.A.values.is_complex():
+            # the captured cycle is validated for the real modes only: the
+            # complex modes run the eager cycle, and asking for the graph
+            # is an error
+            if self._graph_requested and self.res.is_cuda:
+                raise NotImplementedError(
+                    "the hipGraph cycle (hipgraph_cycle / use_hip_graph = 1)"
+                    " is not available in the complex modes")
+            self.use_graph = False
         reuse = int(self.scope.get("structure_reuse_levels") or 0)
         old = getattr(self, "hierarchy", None)
         if (reuse != 0 and old is not None and old.levels

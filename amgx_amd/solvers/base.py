@@ -162,6 +162,13 @@ class Solver:
     def solver_setup(self):
         pass
 
+    def _real_only(self, feature: str):
+        """Refuse a complex matrix (modes ?ZZI / ?CCI / ?ZCI) in a solver
+        whose arithmetic is real; called first in its solver_setup."""
+        if self.A is not None and self.A.values.is_complex():
+            raise NotImplementedError(
+                f"{feature} is not available in the complex modes")
+
     # -- norms ---------------------------------------------------------------
     def _owned(self, x: torch.Tensor) -> torch.Tensor:
         """Owned prefix of a (possibly halo-extended) distributed vector

@@ -24,10 +24,16 @@ class DenseLUSolver(Solver):
     def solver_setup(self):
         A = self.A
         m = A.to_scipy()
-        dense = np.asarray(m.todense(), dtype=np.float64)
+        # invert in the matrix's own field: complex128 for a complex matrix
+        # (modes ?ZZI / ?CCI / ?ZCI), float64 for a real one
+        work = np.complex128 if A.values.is_complex() else np.float64
+        dense = np.asarray(m.todense(), dtype=work)
         n = dense.shape[0]
         if n == 0:
-            self.Ainv = torch.zeros((0, 0), dtype=torch.float64, device=A.device)
+            self.Ainv = torch.zeros(
+                (0, 0), device=A.device,
+                dtype=A.values.dtype if A.values.is_complex()
+                else torch.float64)
             return
         # regularize exactly singular coarse systems (all-Neumann problems)
         try:
@@ -62,6 +68,10 @@ class GatheredDenseLU:
 
     def setup(self, A):
         import torch.distributed as tdist
+        if A.values.is_complex():
+            raise NotImplementedError(
+                "the distributed (gathered) dense coarse solve is not "
+                "available in the complex modes")
         mgr = A.manager
         self.mgr = mgr
         n_g = mgr.global_rows(mgr.n_local)

@@ -37,6 +37,8 @@ class MulticolorDILUSolver(_SmootherBase):
 
     def solver_setup(self):
         A = self.A
+        if A.block_dim != 1:
+            self._real_only("MULTICOLOR_DILU on a block matrix")
         if A.coloring is None:
             from ..amg.coloring import MatrixColoring
             A.coloring = MatrixColoring.create(A, self.scope)

@@ -70,6 +70,7 @@ class MulticolorILUSolver(_SmootherBase):
 
     def solver_setup(self):
         A = self.A
+        self._real_only("MULTICOLOR_ILU")
         if self.sparsity_level > 0 and A.block_dim != 1:
             raise NotImplementedError(
                 "ILU(k>0) fill patterns are scalar-only (block ILU(0) is "

@@ -37,6 +37,7 @@ class KaczmarzSolver(_SmootherBase):
 
     def solver_setup(self):
         A = self.A
+        self._real_only("KACZMARZ")
         # Kaczmarz scatters into the COLUMNS of each row: parallel same-color
         # updates need rows that share no column, i.e. a DISTANCE-2 coloring
         # (reference: kaczmarz pairs with LOCALLY_DOWNWIND / 2-ring
@@ -122,6 +123,7 @@ class CFJacobiSolver(_SmootherBase):
 
     def solver_setup(self):
         A = self.A
+        self._real_only("CF_JACOBI")
         self.dinv = ops.jacobi_dinv(A)
         cf = A._cache.get("cf_map")
         if cf is None:

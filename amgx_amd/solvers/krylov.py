@@ -341,6 +341,8 @@ class IDRSolver(Solver):
         self.s = scope.get("subspace_dim_s")
 
     def solver_setup(self):
+        # the shadow space and the small systems of this variant are real
+        self._real_only("IDR")
         # keep the preconditioner object across resetup so its hierarchy can
         # honor structure_reuse_levels (reference AMGX_solver_resetup)
         if getattr(self, "precond", None) is None:

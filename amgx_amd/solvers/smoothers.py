@@ -75,6 +75,8 @@ class BlockJacobiSolver(_SmootherBase):
     l1 = False
 
     def solver_setup(self):
+        if self.A.block_dim != 1:
+            self._real_only("BLOCK_JACOBI on a block matrix")
         self.dinv = ops.jacobi_dinv(self.A, l1=self.l1)
         # Spectral safeguard: Galerkin (D2) coarse operators can reach
         # lam_max(D^-1 A) ~ 4, where the fixed 0.9 damping DIVERGES as a
@@ -117,6 +119,7 @@ class JacobiL1Solver(_SmootherBase):
             self.relaxation_factor = 1.0
 
     def solver_setup(self):
+        self._real_only("JACOBI_L1")
         self.dinv = ops.jacobi_dinv(self.A, l1=True)
 
     def solve_iteration(self, b, x):
@@ -140,6 +143,10 @@ class MulticolorGSSolver(_SmootherBase):
 
     def solver_setup(self):
         A = self.A
+        if A.block_dim != 1:
+            self._real_only("MULTICOLOR_GS on a block matrix")
+        if self.scope.get("GS_L1_variant"):
+            self._real_only("GS_L1_variant")
         if A.coloring is None:
             from ..amg.coloring import MatrixColoring
             A.coloring = MatrixColoring.create(A, self.scope)
@@ -205,6 +212,7 @@ class ChebyshevSolver(_SmootherBase):
         self.est_mode = scope.get("chebyshev_lambda_estimate_mode")
 
     def solver_setup(self):
+        self._real_only("The Chebyshev / polynomial smoother family")
         self.dinv = ops.jacobi_dinv(self.A, l1=True)
         if self.est_mode in (0, 1):
             self.lmax = self._power_iteration(16)
