@@ -184,7 +184,8 @@ class AMGHierarchy:
         "relaxation_factor", "symmetric_GS", "GS_L1_variant",
         "jacobi_l1_variant", "matrix_coloring_scheme", "coloring_level",
         "max_uncolored_percentage", "num_colors", "max_num_hash",
-        "ilu_sparsity_level", "chebyshev_polynomial_order",
+        "ilu_sparsity_level", "ilu_fill_pattern",
+        "chebyshev_polynomial_order",
         "chebyshev_lambda_estimate_mode", "cheby_max_lambda",
         "cheby_min_lambda", "kpz_order", "cf_smoothing_mode")
 

@@ -129,7 +129,14 @@ def _register_core_parameters() -> None:
     P("jacobi_l1_variant", int, 0, "L1 Jacobi variant")
     P("symmetric_GS", int, 0, "symmetric Gauss-Seidel sweeps")
     P("GS_L1_variant", int, 0, "L1 variant of Gauss-Seidel")
-    P("ilu_sparsity_level", int, 0, "ILU(k) level (0 or 1)")
+    P("ilu_sparsity_level", int, 0,
+      "ILU(k) fill level: 0, 1, or higher with ilu_fill_pattern=POWER "
+      "(scalar matrices)")
+    P("ilu_fill_pattern", str, "AUTO",
+      "ILU(k>0) pattern: COLORED = fill of the color-ordered elimination "
+      "under A's own coloring (level 1, scalar and block), POWER = "
+      "pattern(A^(k+1)) re-colored (scalar), AUTO = POWER for scalar and "
+      "COLORED for block matrices", ("AUTO", "POWER", "COLORED"))
     P("kaczmarz_coloring_needed", int, 1, "accepted for parity")
     P("cf_smoothing_mode", int, 0,
       "CF-Jacobi sweep order: 0=CF pre / FC post, 1=opposite "

@@ -239,6 +239,59 @@ std::vector<Tensor> spgemm_hash(Tensor roA, Tensor ciA, Tensor vaA,
     return {roC, ciC.narrow(0, 0, nnz), vaC.narrow(0, 0, nnz), big};
 }
 
+// Color-aware ILU(1) fill pattern of (ro, ci) under the row coloring `colors`
+// (kernels_spgemm.hip).  Returns (roL, ciL, big_rows): big_rows lists rows
+// written unsorted (the Python caller sorts those).  Empty ciL + roL[-1]==-1
+// signals "a row exceeded ILU1_TOP_CAP, build the pattern on the host".
+std::vector<Tensor> ilu1_pattern(Tensor ro, Tensor ci, Tensor colors,
+                                 int64_t n) {
+    check_dev(ro);
+    TORCH_CHECK(ro.numel() == n + 1 && colors.numel() == n,
+                "ilu1_pattern: ro / colors do not have n rows");
+    auto roL = torch::empty({n + 1}, ro.options());
+    auto big = torch::empty({0}, ro.options());
+    hipStream_t st = cur_stream();
+    amgx_hip::Ilu1Tiers tiers;
+    long long nnz = amgx_hip::ilu1_pattern_count(
+        iptr(ro), iptr(ci), iptr(colors), (int)n, iptr(roL), &tiers, st);
+    if (nnz < 0) {
+        roL.fill_(-1);
+        return {roL, torch::empty({0}, ro.options()), big};
+    }
+    auto ciL = torch::empty({(int64_t)nnz}, ro.options());
+    amgx_hip::ilu1_pattern_fill(iptr(ro), iptr(ci), iptr(colors), (int)n,
+                                iptr(roL), iptr(ciL), tiers, st);
+    if (tiers.n_big > 0) {
+        big = torch::empty({tiers.n_big}, ro.options());
+        TORCH_CHECK(hipMemcpyAsync(iptr(big), tiers.big_rows,
+                                   tiers.n_big * sizeof(int),
+                                   hipMemcpyDeviceToDevice, st) == hipSuccess,
+                    "ilu1_pattern: big_rows copy failed");
+    }
+    amgx_hip::ilu1_tiers_free(&tiers, st);
+    return {roL, ciL, big};
+}
+
+// A's values at their slots of the sorted pattern (roL, ciL), zeros in the
+// fill slots: returns (values (nnzL * bb), a_to_lu (nnzA) int32)
+std::vector<Tensor> ilu1_embed(Tensor roA, Tensor ciA, Tensor vaA, int64_t bb,
+                               Tensor roL, Tensor ciL) {
+    check_dev(vaA);
+    int n = (int)roA.numel() - 1;
+    int64_t nnzA = ciA.numel();
+    TORCH_CHECK(vaA.numel() == nnzA * bb && roL.numel() == roA.numel(),
+                "ilu1_embed: shapes of A and the pattern disagree");
+    auto vaL = torch::zeros({ciL.numel() * bb}, vaA.options());
+    auto a_to_lu = torch::empty({nnzA}, roA.options());
+    DISPATCH(AMGX_REAL_TYPES, "ilu1_embed", (vaA), [&] {
+        amgx_hip::ilu1_embed<scalar_t>(
+            iptr(roA), iptr(ciA), dptr<scalar_t>(vaA), n, (long long)nnzA,
+            (int)bb, iptr(roL), iptr(ciL), dptr<scalar_t>(vaL),
+            iptr(a_to_lu), cur_stream());
+    });
+    return {vaL, a_to_lu};
+}
+
 Tensor mfma4_probe(Tensor a_frag, Tensor b_frag) {
     auto c = torch::empty_like(a_frag);
     amgx_hip::mfma4_probe(dptr<double>(a_frag), dptr<double>(b_frag),
@@ -822,6 +875,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("axpy_dalpha", &axpy_dalpha);
     m.def("mfma4_probe", &mfma4_probe);
     m.def("spgemm_hash", &spgemm_hash);
+    m.attr("ILU1_TOP_CAP") = amgx_hip::ILU1_TOP_CAP;
+    m.def("ilu1_pattern", &ilu1_pattern);
+    m.def("ilu1_embed", &ilu1_embed);
     m.def("bsrmv_generic", &bsrmv_generic);
     m.def("scal_drsqrt", &scal_drsqrt);
     m.def("axpby", &axpby);

@@ -278,6 +278,38 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
                       int** big_rows_out, int* n_big_out, hipStream_t s);
 void free_device_buf(void* p, hipStream_t s);
 
+// ---- color-aware ILU(1) fill pattern ----------------------------------------
+// Row i of the pattern = A's row i (halo columns included) + i + every local
+// j reached through a local pivot k of A's row i with colors[k] < colors[i],
+// (k, j) in A, colors[j] > colors[k] and colors[j] != colors[i]. Same
+// 64 -> 512 -> top ladder as spgemm_hash; the top tier holds ILU1_TOP_CAP
+// columns (keys only, 32 KB of LDS).
+constexpr int ILU1_TOP_CAP = 8192;
+// device row lists of the upper tiers, produced by the count pass
+struct Ilu1Tiers {
+    int* mid_rows = nullptr;   // rows past the 64 tier
+    int n_mid = 0;
+    int* big_rows = nullptr;   // rows past the 512 tier: written UNSORTED
+    int n_big = 0;
+};
+// count + scan: fills roC_out (n+1) and *tiers, returns the pattern's nnz, or
+// -1 (tiers freed) when a row exceeds ILU1_TOP_CAP
+long long ilu1_pattern_count(const int* ro, const int* ci, const int* colors,
+                             int n, int* roC_out, Ilu1Tiers* tiers,
+                             hipStream_t s);
+// fill: ciC (nnz of the count pass), rows ascending except tiers.big_rows
+void ilu1_pattern_fill(const int* ro, const int* ci, const int* colors, int n,
+                       const int* roC, int* ciC, const Ilu1Tiers& tiers,
+                       hipStream_t s);
+void ilu1_tiers_free(Ilu1Tiers* tiers, hipStream_t s);
+// vaL[a_to_lu[k]] = vaA[k] (bb values each) for every entry k of A, where
+// a_to_lu[k] is the slot of A's entry in the sorted pattern (roL, ciL); vaL is
+// zero-initialised by the caller. Real types.
+template <typename T>
+void ilu1_embed(const int* roA, const int* ciA, const T* vaA, int n,
+                long long nnzA, int bb, const int* roL, const int* ciL,
+                T* vaL, int* a_to_lu, hipStream_t s);
+
 // ============================================================ kernels_classical.hip
 // ---- classical setup -------------------------------------------------------
 template <typename T>

@@ -16,6 +16,9 @@
 // with a 8-16x larger table (80-96 KB LDS); rows beyond THAT fall back to
 // the ESC sort path at the Python dispatch level (rare: >8k nnz per row,
 // >4k for complex128 values).
+//
+// The color-aware ILU(1) fill pattern at the end of the file is a keys-only
+// user of the same hash set, ladder and sort.
 
 #include <cstring>
 
@@ -120,6 +123,39 @@ __device__ __forceinline__ void wave_bitonic(int* k, T* v, int p, int lane) {
     }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
+}
+
+// rows with counts[i] == -1 climb the capacity ladder (rare, setup-time: the
+// overflow-list compaction runs on host). Returns their number and, when
+// non-zero, their device list in *rows_out (caller frees).
+int collect_marked_rows(const int* counts, int m, int** rows_out,
+                        hipStream_t s) {
+    std::vector<int> h_counts(m);
+    HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts, m * sizeof(int),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    std::vector<int> marked;
+    for (int i = 0; i < m; ++i)
+        if (h_counts[i] == -1) marked.push_back(i);
+    int n = (int)marked.size();
+    if (n) {
+        HIP_CHECK(hipMallocAsync(rows_out, n * sizeof(int), s));
+        HIP_CHECK(hipMemcpyAsync(*rows_out, marked.data(), n * sizeof(int),
+                                 hipMemcpyHostToDevice, s));
+    }
+    return n;
+}
+
+// exclusive scan of counts[0, m] (counts[m] == 0) -> row offsets ro_out
+void exclusive_scan_counts(int* counts, int* ro_out, int m, hipStream_t s) {
+    size_t tmp_bytes = 0;
+    (void)rocprim::exclusive_scan(nullptr, tmp_bytes, counts, ro_out, 0,
+                                  m + 1, rocprim::plus<int>(), s);
+    void* tmp = nullptr;
+    HIP_CHECK(hipMallocAsync(&tmp, tmp_bytes, s));
+    (void)rocprim::exclusive_scan(tmp, tmp_bytes, counts, ro_out, 0, m + 1,
+                                  rocprim::plus<int>(), s);
+    HIP_CHECK(hipFreeAsync(tmp, s));
 }
 
 }  // namespace
@@ -283,24 +319,8 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
     HIP_CHECK(hipMemcpyAsync(&h_ovf, ovf, sizeof(int), hipMemcpyDeviceToHost,
                              s));
     HIP_CHECK(hipStreamSynchronize(s));
-    // rows with counts[i] == -1 climb the ladder (rare, setup-time: the
-    // overflow-list compaction runs on host)
     auto collect_marked = [&](int** rows_out) -> int {
-        std::vector<int> h_counts(m);
-        HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts, m * sizeof(int),
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        std::vector<int> marked;
-        for (int i = 0; i < m; ++i)
-            if (h_counts[i] == -1) marked.push_back(i);
-        int n = (int)marked.size();
-        if (n) {
-            HIP_CHECK(hipMallocAsync(rows_out, n * sizeof(int), s));
-            HIP_CHECK(hipMemcpyAsync(*rows_out, marked.data(),
-                                     n * sizeof(int), hipMemcpyHostToDevice,
-                                     s));
-        }
-        return n;
+        return collect_marked_rows(counts, m, rows_out, s);
     };
     int* mid_rows = nullptr;   // rows needing the 512 tier (only if tiny)
     int n_mid = 0;
@@ -335,15 +355,7 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
         }
     }
     HIP_CHECK(hipFreeAsync(ovf, s));
-    // exclusive scan counts -> roC
-    size_t tmp_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, tmp_bytes, counts, roC_out, 0,
-                                  m + 1, rocprim::plus<int>(), s);
-    void* tmp = nullptr;
-    HIP_CHECK(hipMallocAsync(&tmp, tmp_bytes, s));
-    (void)rocprim::exclusive_scan(tmp, tmp_bytes, counts, roC_out, 0, m + 1,
-                                  rocprim::plus<int>(), s);
-    HIP_CHECK(hipFreeAsync(tmp, s));
+    exclusive_scan_counts(counts, roC_out, m, s);
     HIP_CHECK(hipFreeAsync(counts, s));
     int h_nnz = 0;
     HIP_CHECK(hipMemcpyAsync(&h_nnz, roC_out + m, sizeof(int),
@@ -390,6 +402,281 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
 
 #define INSTANTIATE_SPGEMM_HASH(T) AMGX_INSTANTIATE(spgemm_hash, T)
 AMGX_VALUE_TYPES(INSTANTIATE_SPGEMM_HASH)
+
+// ============================================================ ILU(1) pattern
+// Color-aware level-1 fill (role of the reference's csr_sparsity_ilu1,
+// src/csr_multiply_detail.cu:575-749): the pattern keeps A's own coloring c
+// and adds only the fill that color-ordered elimination creates. Row i is
+//   A's row i (halo columns >= n included, unchanged)  +  i itself  +
+//   every j < n with a local pivot k in A's row i (k < n, c[k] < c[i]) such
+//   that (k, j) is in A, c[j] > c[k] and c[j] != c[i].
+// Halo columns are never pivots and never expanded. Same scheme as the
+// SpGEMM above: wave-per-row hash set, count, scan, fill, tier ladder.
+namespace {
+
+// key-only twin of wave_bitonic
+__device__ __forceinline__ void wave_bitonic_keys(int* k, int p, int lane) {
+    for (int size = 2; size <= p; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __builtin_amdgcn_s_waitcnt(0);
+            __builtin_amdgcn_wave_barrier();
+            for (int idx = lane; idx < p / 2; idx += 64) {
+                int half = idx / stride;
+                int lo = half * 2 * stride + (idx % stride);
+                int hi = lo + stride;
+                bool up = ((lo & size) == 0);
+                int ka = k[lo], kb = k[hi];
+                if ((ka > kb) == up) { k[lo] = kb; k[hi] = ka; }
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one wave inserts the pattern of row i into its (cleared) hash set; cnt is
+// this lane's number of new keys, ovf is set when the table filled up
+template <int CAP>
+__device__ __forceinline__ void ilu1_walk_row(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const int* __restrict__ colors, int n, int i, int* keys, int lane,
+    int& cnt, bool& ovf) {
+    int s = ro[i], e = ro[i + 1];
+    int col_i = colors[i];
+    for (int k = s + lane; k < e; k += 64) {
+        int r = hset_insert(keys, CAP, ci[k]);
+        if (r < 0) ovf = true; else cnt += r;
+    }
+    if (lane == 0) {
+        int r = hset_insert(keys, CAP, i);
+        if (r < 0) ovf = true; else cnt += r;
+    }
+    for (int k = s; k < e; ++k) {
+        int p = ci[k];                    // wave-uniform
+        if (p >= n) continue;             // halo column: not a pivot
+        int col_p = colors[p];
+        if (col_p >= col_i) continue;
+        for (int t = ro[p] + lane; t < ro[p + 1]; t += 64) {
+            int j = ci[t];
+            if (j >= n) continue;         // halo column: not expanded
+            int col_j = colors[j];
+            if (col_j > col_p && col_j != col_i) {
+                int r = hset_insert(keys, CAP, j);
+                if (r < 0) ovf = true; else cnt += r;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+template <int CAP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void ilu1_count_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const int* __restrict__ colors, int n, const int* __restrict__ row_list,
+    int n_rows, int* __restrict__ counts, int* __restrict__ overflow) {
+    __shared__ int keys_s[WAVES][CAP];
+    int wave = threadIdx.x / 64;
+    int lane = threadIdx.x & 63;
+    int slot = blockIdx.x * WAVES + wave;
+    if (slot >= n_rows) return;
+    int i = row_list ? row_list[slot] : slot;
+    int* keys = keys_s[wave];
+    for (int t = lane; t < CAP; t += 64) keys[t] = -1;
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    int cnt = 0;
+    bool ovf = false;
+    ilu1_walk_row<CAP>(ro, ci, colors, n, i, keys, lane, cnt, ovf);
+    cnt = (int)wave_reduce_sum(cnt);
+    ovf = __any(ovf);
+    if (lane == 0) {
+        counts[i] = ovf ? -1 : cnt;     // -1 marks the row for a bigger tier
+        if (ovf) atomicExch(overflow, 1);
+    }
+}
+
+// Writes each row's columns ascending (the factor kernels binary-search
+// them).  SORTED=0 keeps the hash order; the caller sorts those rows.
+template <int CAP, int WAVES, int SORTED>
+__global__ __launch_bounds__(64 * WAVES) void ilu1_fill_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const int* __restrict__ colors, int n, const int* __restrict__ row_list,
+    int n_rows, const int* __restrict__ roC, int* __restrict__ ciC) {
+    __shared__ int keys_s[WAVES][CAP];
+    __shared__ int ck_s[WAVES][SORTED ? CAP : 1];
+    __shared__ int cur_s[WAVES];
+    int wave = threadIdx.x / 64;
+    int lane = threadIdx.x & 63;
+    int slot = blockIdx.x * WAVES + wave;
+    if (slot >= n_rows) return;
+    int i = row_list ? row_list[slot] : slot;
+    long long base = roC[i];
+    int count = (int)((long long)roC[i + 1] - base);
+    // rows beyond this kernel's capacity are handled by the next tier
+    if (count > CAP) return;
+    int* keys = keys_s[wave];
+    for (int t = lane; t < CAP; t += 64) keys[t] = -1;
+    if (lane == 0) cur_s[wave] = 0;
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    int cnt = 0;
+    bool ovf = false;
+    ilu1_walk_row<CAP>(ro, ci, colors, n, i, keys, lane, cnt, ovf);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (SORTED) {
+        int* ck = ck_s[wave];
+        for (int t = lane; t < CAP; t += 64) {
+            if (keys[t] != -1) {
+                int dst = atomicAdd(&cur_s[wave], 1);
+                ck[dst] = keys[t];
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        int p = 1;
+        while (p < count) p <<= 1;
+        for (int t = count + lane; t < p; t += 64) ck[t] = 0x7fffffff;
+        wave_bitonic_keys(ck, p, lane);
+        for (int t = lane; t < count; t += 64) ciC[base + t] = ck[t];
+    } else {
+        for (int t = lane; t < CAP; t += 64) {
+            if (keys[t] != -1) {
+                int dst = atomicAdd(&cur_s[wave], 1);
+                ciC[base + dst] = keys[t];
+            }
+        }
+    }
+}
+
+long long ilu1_pattern_count(const int* ro, const int* ci, const int* colors,
+                             int n, int* roC_out, Ilu1Tiers* tiers,
+                             hipStream_t s) {
+    *tiers = Ilu1Tiers{};
+    int* counts = nullptr;
+    HIP_CHECK(hipMallocAsync(&counts, (n + 1) * sizeof(int), s));
+    int* ovf = nullptr;
+    HIP_CHECK(hipMallocAsync(&ovf, sizeof(int), s));
+    HIP_CHECK(hipMemsetAsync(ovf, 0, sizeof(int), s));
+    HIP_CHECK(hipMemsetAsync(counts, 0, (n + 1) * sizeof(int), s));
+    auto overflowed = [&]() -> bool {
+        int h_ovf = 0;
+        HIP_CHECK(hipMemcpyAsync(&h_ovf, ovf, sizeof(int),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipMemsetAsync(ovf, 0, sizeof(int), s));
+        return h_ovf != 0;
+    };
+    if (n > 0)
+        hipLaunchKernelGGL((ilu1_count_kernel<TINY_CAP, 8>),
+                           dim3((n + 7) / 8), dim3(64 * 8), 0, s, ro, ci,
+                           colors, n, nullptr, n, counts, ovf);
+    bool too_wide = false;
+    if (overflowed()) {
+        tiers->n_mid = collect_marked_rows(counts, n, &tiers->mid_rows, s);
+        hipLaunchKernelGGL((ilu1_count_kernel<SMALL_CAP, 4>),
+                           dim3((tiers->n_mid + 3) / 4), dim3(64 * 4), 0, s,
+                           ro, ci, colors, n, tiers->mid_rows, tiers->n_mid,
+                           counts, ovf);
+        if (overflowed()) {
+            tiers->n_big = collect_marked_rows(counts, n, &tiers->big_rows,
+                                               s);
+            hipLaunchKernelGGL((ilu1_count_kernel<ILU1_TOP_CAP, 1>),
+                               dim3(tiers->n_big), dim3(64), 0, s, ro, ci,
+                               colors, n, tiers->big_rows, tiers->n_big,
+                               counts, ovf);
+            too_wide = overflowed();
+        }
+    }
+    HIP_CHECK(hipFreeAsync(ovf, s));
+    if (too_wide) {      // a row wider than the top tier: host builder
+        HIP_CHECK(hipFreeAsync(counts, s));
+        ilu1_tiers_free(tiers, s);
+        return -1;
+    }
+    exclusive_scan_counts(counts, roC_out, n, s);
+    HIP_CHECK(hipFreeAsync(counts, s));
+    int h_nnz = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_nnz, roC_out + n, sizeof(int),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return (long long)h_nnz;
+}
+
+void ilu1_pattern_fill(const int* ro, const int* ci, const int* colors, int n,
+                       const int* roC, int* ciC, const Ilu1Tiers& tiers,
+                       hipStream_t s) {
+    // as in spgemm_hash, each kernel's per-row guard skips rows bigger than
+    // its table and the next tier writes them
+    if (n > 0)
+        hipLaunchKernelGGL((ilu1_fill_kernel<TINY_CAP, 8, 1>),
+                           dim3((n + 7) / 8), dim3(64 * 8), 0, s, ro, ci,
+                           colors, n, nullptr, n, roC, ciC);
+    if (tiers.n_mid)
+        hipLaunchKernelGGL((ilu1_fill_kernel<SMALL_CAP, 4, 1>),
+                           dim3((tiers.n_mid + 3) / 4), dim3(64 * 4), 0, s,
+                           ro, ci, colors, n, tiers.mid_rows, tiers.n_mid,
+                           roC, ciC);
+    if (tiers.n_big)
+        hipLaunchKernelGGL((ilu1_fill_kernel<ILU1_TOP_CAP, 1, 0>),
+                           dim3(tiers.n_big), dim3(64), 0, s, ro, ci, colors,
+                           n, tiers.big_rows, tiers.n_big, roC, ciC);
+}
+
+void ilu1_tiers_free(Ilu1Tiers* tiers, hipStream_t s) {
+    if (tiers->mid_rows) HIP_CHECK(hipFreeAsync(tiers->mid_rows, s));
+    if (tiers->big_rows) HIP_CHECK(hipFreeAsync(tiers->big_rows, s));
+    *tiers = Ilu1Tiers{};
+}
+
+// One thread per value element of A: entry k = t / bb finds its row by
+// bisection of the row offsets and its column in the sorted LU row, copies
+// its element and (element 0) records the slot in a_to_lu.
+template <typename T>
+__global__ __launch_bounds__(AMGX_BLOCK) void ilu1_embed_kernel(
+    const int* __restrict__ roA, const int* __restrict__ ciA,
+    const T* __restrict__ vaA, int n, long long total, int bb,
+    const int* __restrict__ roL, const int* __restrict__ ciL,
+    T* __restrict__ vaL, int* __restrict__ a_to_lu) {
+    long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         t < total; t += stride) {
+        int k = (int)(t / bb);
+        int q = (int)(t - (long long)k * bb);
+        int lo = 0, hi = n;          // roA[lo] <= k < roA[hi]
+        while (hi - lo > 1) {
+            int mid = (lo + hi) >> 1;
+            if (roA[mid] <= k) lo = mid; else hi = mid;
+        }
+        int col = ciA[k];
+        int slot = -1;
+        int a = roL[lo], b = roL[lo + 1];
+        while (a < b) {
+            int mid = (a + b) >> 1;
+            int c = ciL[mid];
+            if (c == col) { slot = mid; break; }
+            if (c < col) a = mid + 1; else b = mid;
+        }
+        if (slot >= 0) vaL[(long long)slot * bb + q] = vaA[t];
+        if (q == 0) a_to_lu[k] = slot;
+    }
+}
+
+template <typename T>
+void ilu1_embed(const int* roA, const int* ciA, const T* vaA, int n,
+                long long nnzA, int bb, const int* roL, const int* ciL,
+                T* vaL, int* a_to_lu, hipStream_t s) {
+    long long total = nnzA * bb;
+    if (total == 0) return;
+    hipLaunchKernelGGL((ilu1_embed_kernel<T>),
+                       dim3(grid_1d(total, AMGX_BLOCK, 2048)),
+                       dim3(AMGX_BLOCK), 0, s, roA, ciA, vaA, n, total, bb,
+                       roL, ciL, vaL, a_to_lu);
+}
+
+#define INSTANTIATE_ILU1_EMBED(T) AMGX_INSTANTIATE(ilu1_embed, T)
+AMGX_REAL_TYPES(INSTANTIATE_ILU1_EMBED)
 
 void free_device_buf(void* p, hipStream_t s) {
     HIP_CHECK(hipFreeAsync(p, s));

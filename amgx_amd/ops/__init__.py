@@ -230,6 +230,14 @@ def dilu_solve(A, Einv, coloring, r, relaxation, x):
     return _backend(A).dilu_solve(A, Einv, coloring, r, relaxation, x)
 
 
+# ---------------------------------------------------------------------- ILU(1)
+def ilu1_pattern(A, coloring):
+    """Color-aware level-1 ILU fill pattern of A under `coloring`, A's values
+    embedded and zeros in the fill slots (reference csr_sparsity_ilu1,
+    src/csr_multiply_detail.cu). The result keeps A's coloring."""
+    return _backend(A).ilu1_pattern(A, coloring)
+
+
 # ---------------------------------------------------------------------- dense
 def dense_solve(Ainv, b, x):
     """x = Ainv @ b — small dense coarse solve (reference

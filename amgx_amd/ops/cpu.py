@@ -800,6 +800,48 @@ def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):
     return x
 
 
+# ---------------------------------------------------------------------- ILU(1)
+def ilu1_pattern(A, coloring):
+    """Color-aware level-1 fill pattern (reference csr_sparsity_ilu1): A's
+    pattern plus the diagonal plus the fill that elimination in the order of
+    `coloring` creates, as a CSRMatrix with A's values embedded and zeros in
+    the new slots. Entry (i, j), j local, is fill when a local pivot k has
+    (i, k) and (k, j) in A with c[k] < c[i], c[j] > c[k] and c[j] != c[i].
+    Halo columns (>= n_rows) are kept but are neither pivots nor expanded.
+
+    Host builder and parity oracle of the device kernels: the fill is one
+    boolean product of the color-masked strict parts, L = {c[col] < c[row]}
+    times U = {c[col] > c[row]}."""
+    from ..matrix import CSRMatrix
+    n, nc = A.n_rows, max(A.n_cols, A.n_rows)
+    ro = A.row_offsets.cpu().numpy().astype(np.int64)
+    ci = A.col_indices.cpu().numpy().astype(np.int64)
+    c = coloring.colors.cpu().numpy().astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ro))
+    loc = ci < n
+    r, k = rows[loc], ci[loc]
+
+    def mask(sel):
+        return sp.csr_matrix((np.ones(int(sel.sum()), dtype=np.int32),
+                              (r[sel], k[sel])), shape=(n, n))
+
+    F = (mask(c[k] < c[r]) @ mask(c[k] > c[r])).tocoo()
+    keep = c[F.col] != c[F.row]
+    a_keys = rows * nc + ci
+    diag = np.arange(n, dtype=np.int64)
+    keys = np.unique(np.concatenate([
+        a_keys, diag * nc + diag,
+        F.row[keep].astype(np.int64) * nc + F.col[keep]]))
+    ro_f = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys // nc, minlength=n), out=ro_f[1:])
+    va = A.values.cpu()
+    va_f = torch.zeros((keys.size,) + tuple(va.shape[1:]), dtype=va.dtype)
+    va_f[torch.from_numpy(np.searchsorted(keys, a_keys))] = va
+    return CSRMatrix(torch.from_numpy(ro_f.astype(np.int32)),
+                     torch.from_numpy((keys % nc).astype(np.int32)), va_f,
+                     n_cols=A.n_cols, block_dim=A.block_dim)
+
+
 # ---------------------------------------------------------------------- classical
 def strength_ahat(A, theta: float = 0.25, max_row_sum: float = 1.1):
     """AHAT strength mask aligned with A's CSR entries: strong iff

@@ -445,13 +445,14 @@ def _expansion_bound(A, B):
 
 def _sort_unsorted_rows(ro, ci, va, big_rows):
     """Column-sort the (rare) rows the top-tier hash kernel wrote
-    unsorted (>512 nnz per row)."""
+    unsorted (>512 nnz per row); va is None for a pattern without values."""
     ro64 = ro.to(torch.int64)
     for r in big_rows.tolist():
         s, e = int(ro64[r]), int(ro64[r + 1])
         order = torch.argsort(ci[s:e])
         ci[s:e] = ci[s:e][order]
-        va[s:e] = va[s:e][order]
+        if va is not None:
+            va[s:e] = va[s:e][order]
 
 
 def spgemm(A, B):
@@ -548,6 +549,28 @@ def ilu0_setup(A, coloring):
     lu = _core.ilu0_setup(A.row_offsets, A.col_indices, A.values, _didx(A),
                           pos, coloring.rows_sorted, coloring.bounds)
     return lu
+
+
+def ilu1_pattern(A, coloring):
+    """Color-aware ILU(1) fill pattern with A's values embedded (see
+    ops/cpu.py ilu1_pattern for the rule): LDS-hash count/fill kernels plus
+    the embed kernel of kernels_spgemm.hip. A row wider than the top hash
+    tier (ILU1_TOP_CAP columns) sends the whole build to the host builder."""
+    from ..matrix import CSRMatrix
+    colors = coloring.colors.to(torch.int32).contiguous()
+    ro, ci, big = _core.ilu1_pattern(A.row_offsets, A.col_indices, colors,
+                                     A.n_rows)
+    if int(ro[0].item()) == -1:
+        from . import cpu
+        return cpu.ilu1_pattern(A.to("cpu"), coloring).to(A.device)
+    if big.numel():
+        _sort_unsorted_rows(ro, ci, None, big)
+    bb = A.block_dim * A.block_dim
+    va, _ = _core.ilu1_embed(A.row_offsets, A.col_indices,
+                             A.values.reshape(-1), bb, ro, ci)
+    if A.block_dim != 1:
+        va = va.reshape(-1, A.block_dim, A.block_dim)
+    return CSRMatrix(ro, ci, va, n_cols=A.n_cols, block_dim=A.block_dim)
 
 
 def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):

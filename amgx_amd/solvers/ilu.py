@@ -1,4 +1,4 @@
-"""Multicolor ILU(0) smoother/preconditioner.
+"""Multicolor ILU(0) / ILU(k) smoother/preconditioner.
 
 Reference: src/solvers/multicolor_ilu_solver.cu (2,222 LoC, 8 kernels):
 ILU(0) factorization in COLOR order with color-parallel triangular solves.
@@ -6,6 +6,11 @@ ILU(0) factorization in COLOR order with color-parallel triangular solves.
 eliminated in parallel (they cannot couple through a valid distance-1
 coloring for the L/U pattern... coupling happens only via earlier colors;
 same-color coupling is dropped exactly as the reference does).
+
+ilu_sparsity_level > 0 factors on a wider pattern, chosen by
+ilu_fill_pattern: COLORED keeps A's coloring and adds the level-1 fill of
+the color-ordered elimination (ops.ilu1_pattern, scalar and block, on device
+in the d* modes); POWER takes pattern(A^(k+1)) and colors that (scalar).
 """
 
 from __future__ import annotations
@@ -67,25 +72,48 @@ class MulticolorILUSolver(_SmootherBase):
     def __init__(self, scope, resources):
         super().__init__(scope, resources)
         self.sparsity_level = int(scope.get("ilu_sparsity_level") or 0)
+        self.fill_pattern = str(scope.get("ilu_fill_pattern") or "AUTO")
+        if self.fill_pattern not in ("AUTO", "POWER", "COLORED"):
+            raise ValueError(
+                f"ilu_fill_pattern={self.fill_pattern!r}: expected AUTO, "
+                "POWER or COLORED")
+
+    def _fill_pattern(self, A):
+        """POWER or COLORED for this matrix; raises for the combinations
+        neither pattern covers."""
+        pattern = self.fill_pattern
+        if pattern == "AUTO":
+            pattern = "POWER" if A.block_dim == 1 else "COLORED"
+        if pattern == "POWER" and A.block_dim != 1:
+            raise NotImplementedError(
+                "ilu_fill_pattern=POWER is scalar-only; block matrices take "
+                "ILU(1) with ilu_fill_pattern=COLORED (or AUTO)")
+        if pattern == "COLORED" and self.sparsity_level >= 2:
+            raise NotImplementedError(
+                "ilu_fill_pattern=COLORED stops at ilu_sparsity_level=1, the "
+                "limit of the reference's csr_sparsity_ilu1; higher levels "
+                "need ilu_fill_pattern=POWER (scalar matrices)")
+        return pattern
 
     def solver_setup(self):
         A = self.A
         self._real_only("MULTICOLOR_ILU")
-        if self.sparsity_level > 0 and A.block_dim != 1:
-            raise NotImplementedError(
-                "ILU(k>0) fill patterns are scalar-only (block ILU(0) is "
-                "supported on host modes)")
-        if self.sparsity_level > 0:
-            # ILU(k): factor on the extended pattern; coloring computed on
-            # that pattern so same-color rows stay decoupled (reference
-            # ilu1_coloringA semantics)
+        from ..amg.coloring import MatrixColoring
+        if self.sparsity_level > 0 and self._fill_pattern(A) == "COLORED":
+            # ILU(1) under A's own coloring: only the fill the color-ordered
+            # elimination creates (reference csr_sparsity_ilu1); no re-coloring
+            if A.coloring is None:
+                A.coloring = MatrixColoring.create(A, self.scope)
+            self.A_f = ops.ilu1_pattern(A, A.coloring)
+            self.A_f.coloring = A.coloring
+        elif self.sparsity_level > 0:
+            # ILU(k) on pattern(A^(k+1)); coloring computed on that pattern
+            # so same-color rows stay decoupled
             self.A_f = extended_sparsity(A, self.sparsity_level)
-            from ..amg.coloring import MatrixColoring
             self.A_f.coloring = MatrixColoring.create(self.A_f, self.scope)
         else:
             self.A_f = A
             if A.coloring is None:
-                from ..amg.coloring import MatrixColoring
                 A.coloring = MatrixColoring.create(A, self.scope)
         self.factors = ilu0_setup(self.A_f, self.A_f.coloring)
 
