@@ -702,7 +702,16 @@ Tensor pmis_select(Tensor ro, Tensor ci, Tensor tidx, Tensor strong,
     amgx_hip::pmis_mark_isolated(iptr(ro), iptr(ci), iptr(tidx),
                                  dptr<unsigned char>(strong), n,
                                  dptr<signed char>(state), st);
-    for (int round = 0; round < max_rounds; ++round) {
+    // Rounds run until no point is left undecided. The counter is taken
+    // between the two halves of a round, so it may still count points that
+    // the second half turns into F: after max_rounds rounds (the host's
+    // guard) the state itself says whether the selection has failed.
+    for (int64_t round = 0;; ++round) {
+        if (round >= max_rounds) {
+            TORCH_CHECK(!state.eq(0).any().item<bool>(),
+                        "PMIS failed to converge in ", max_rounds, " rounds");
+            break;
+        }
         counter.zero_();
         amgx_hip::pmis_one_round(
             iptr(ro), iptr(ci), iptr(tidx), dptr<unsigned char>(strong), n,

@@ -60,9 +60,12 @@ void strength_ahat(const int* ro, const int* ci, const T* va, const int* didx,
 }
 
 // ============================================================ PMIS
-// Strong graph = S union S^T via the transpose-entry index. lambda_i =
-// #strong dependents. One round: undecided local maxima of (lambda + hash)
-// become C; undecided strong neighbors of new C become F.
+// Strong graph = S union S^T via the transpose-entry index: a neighbor j of
+// i is seen only through a stored entry (i, j), so the caller passes a
+// pattern in which every strong (j, i) has one (ops/gpu.py adds them where
+// A's pattern is not symmetric). lambda_i = #strong dependents. One round:
+// undecided local maxima of (lambda + hash) become C; undecided strong
+// neighbors of new C become F.
 __device__ __forceinline__ unsigned int pmis_hash(unsigned int a) {
     a = (a ^ 61u) ^ (a >> 16);
     a *= 9u;
@@ -195,7 +198,8 @@ __global__ __launch_bounds__(AMGX_BLOCK) void d1_count(const int* __restrict__ r
 // fill pass: direct interpolation with pos/neg splitting (reference
 // src/classical/interpolators/distance1.cu):
 //   alpha = sum_neg(all) / sum_neg(strong C), beta likewise for positives;
-//   positives lumped into the diagonal when no positive C connection.
+//   positives lumped into the diagonal when no positive C connection;
+//   a row whose diagonal is zero after that lumping gets zero weights.
 template <typename T>
 __global__ __launch_bounds__(AMGX_BLOCK) void d1_fill(const int* __restrict__ ro, const int* __restrict__ ci,
                         const T* __restrict__ va,
@@ -223,8 +227,10 @@ __global__ __launch_bounds__(AMGX_BLOCK) void d1_fill(const int* __restrict__ ro
             if (a < 0) neg_c += a; else pos_c += a;
         }
     }
+    if (pos_c == 0.0) { diag += pos_all; pos_all = 0.0; }
     if (diag == 0.0) {
-        // degenerate row: emit zero weights for its counted slots
+        // degenerate row (zero diagonal after lumping, as on the host):
+        // emit zero weights for its counted slots
         for (int k = s; k < e; ++k) {
             if (ci[k] == i || !strong[k] || ci[k] >= ncols || cf[ci[k]] < 0)
                 continue;
@@ -234,7 +240,6 @@ __global__ __launch_bounds__(AMGX_BLOCK) void d1_fill(const int* __restrict__ ro
         }
         return;
     }
-    if (pos_c == 0.0) { diag += pos_all; pos_all = 0.0; }
     double alpha = neg_c != 0.0 ? neg_all / neg_c : 0.0;
     double beta = pos_c != 0.0 ? pos_all / pos_c : 0.0;
     for (int k = s; k < e; ++k) {

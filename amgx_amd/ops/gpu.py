@@ -517,10 +517,50 @@ def strength_ahat(A, theta=0.25, max_row_sum=1.1):
                                _didx(A), float(theta), float(max_row_sum))
 
 
-def pmis_select(A, S):
-    state = _core.pmis_select(A.row_offsets, A.col_indices, _tidx(A), S, 64)
-    cmask = state == 1
+def _pmis_graph(A, S):
+    """(row_offsets, col_indices, tidx, strong) the PMIS kernels walk. They
+    reach a neighbour j of i only through a stored entry (i, j) and its
+    transpose index, which is all of S union S^T as long as every strong
+    (j, i) has a stored (i, j). Where one has not (a nonsymmetric pattern),
+    the kernels get the pattern of S union S^T itself, an entry flagged
+    strong iff it is strong in S, so lambda and the neighbourhoods are those
+    of the host."""
     n = A.n_rows
+    ci, tidx = A.col_indices, _tidx(A)
+    sym = A._cache.get("tidx_complete")
+    if sym is None:     # the diagonal's transpose index is itself, never -1
+        sym = not bool(((tidx < 0) & (ci < n)).any().item())
+        A._cache["tidx_complete"] = sym
+    if sym:
+        return A.row_offsets, ci, tidx, S
+    one_way = (S != 0) & (tidx < 0) & (ci < n)
+    if not bool(one_way.any().item()):
+        return A.row_offsets, ci, tidx, S
+    dev = A.device
+    ro64 = A.row_offsets.to(torch.int64)
+    rows = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.int64, device=dev), ro64[1:] - ro64[:-1])
+    ci64 = ci.to(torch.int64)
+    sel = (S != 0) & (ci64 != rows) & (ci64 < n)
+    r, c = rows[sel], ci64[sel]
+    uk, inv = torch.unique(torch.cat([r * n + c, c * n + r]),
+                           return_inverse=True)
+    flag = torch.zeros(uk.numel(), dtype=torch.uint8, device=dev)
+    flag[inv[:r.numel()]] = 1
+    g_ro = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    g_ro[1:] = torch.cumsum(torch.bincount(uk // n, minlength=n),
+                            0).to(torch.int32)
+    g_ci = (uk % n).to(torch.int32).contiguous()
+    return g_ro, g_ci, _core.trans_index(g_ro, g_ci, n), flag
+
+
+def pmis_select(A, S):
+    n = A.n_rows
+    # the host's round guard: past it the binding raises, it never returns
+    # undecided points
+    guard = 8 * (int(math.log2(n + 2)) + 8)
+    state = _core.pmis_select(*_pmis_graph(A, S), guard)
+    cmask = state == 1
     cf = torch.full((n,), -1, dtype=torch.int32, device=A.device)
     csum = torch.cumsum(cmask.to(torch.int64), 0)
     cf[cmask] = (csum[cmask] - 1).to(torch.int32)
