@@ -36,6 +36,9 @@ class AMGHierarchy:
         self.coarsen_threshold = scope.get("coarsen_threshold")
         self.cycle_iters = scope.get("cycle_iters")
         self.print_grid_stats = bool(scope.get("print_grid_stats"))
+        # restrict b itself where the residual would be b - A 0
+        self._skip_zero_residual = \
+            int(scope.get("error_scaling") or 0) not in (2, 3)
         self.setup_time = 0.0
         from ..utils.profiler import PhaseProfiler
         self.profiler = PhaseProfiler(
@@ -323,6 +326,9 @@ class AMGHierarchy:
         if li == len(self.levels) - 1:
             prof.tic("coarseSolve")
             if self.coarse_solver is not None:
+                if zero_guess and getattr(level.A, "manager", None) is not None:
+                    # the gathered solve writes the owned prefix only
+                    x.zero_()
                 self.coarse_solver.solve(b, x, zero_initial_guess=True)
             else:
                 if zero_guess:
@@ -341,11 +347,19 @@ class AMGHierarchy:
             prof.tic("Smoother")
             level.smoother.sweep(b, x, pre)
             prof.toc("Smoother")
-        prof.tic("computeResidual")
-        ops.residual(level.A, x, b, level.r)
-        prof.toc("computeResidual")
+        r = level.r
+        if zero_guess and pre <= 0 and self._skip_zero_residual:
+            # x = 0 and nothing has smoothed it: b - A x is b itself, and
+            # every restriction reads the owned prefix only. error_scaling
+            # 2 / 3 reads level.r again in the scaled prolongation and
+            # keeps the residual.
+            r = b
+        else:
+            prof.tic("computeResidual")
+            ops.residual(level.A, x, b, level.r)
+            prof.toc("computeResidual")
         prof.tic("restrictResidual")
-        level.restrict_residual(level.r, level.bc)
+        level.restrict_residual(r, level.bc)
         prof.toc("restrictResidual")
         if ctype in ("CG", "CGF"):
             # K-cycle (reference src/cycles/cg_cycle.cu + cg_flex_cycle.cu):
@@ -359,7 +373,7 @@ class AMGHierarchy:
             # (reference src/cycles/{v,w,f}_cycle.cu)
             repeats = 2 if ctype in ("W", "F") and li + 2 < len(self.levels) \
                 else 1
-            level.xc.zero_()
+            # the first visit has a zero guess and zeroes xc itself
             for rep in range(repeats):
                 sub = "V" if (ctype == "F" and rep > 0) else ctype
                 self._cycle(li + 1, level.bc, level.xc, rep == 0, sub)

@@ -233,10 +233,9 @@ class AggregationLevel(AMGLevel):
         return Ac
 
     def restrict_residual(self, r, bc):
-        out = ops.restrict_agg(r, self.aggregates, self.num_aggregates,
-                               self.A.block_dim,
-                               structure=getattr(self, "r_structure", None))
-        bc.reshape(-1)[:out.numel()].copy_(out.reshape(-1))
+        ops.restrict_agg(r, self.aggregates, self.num_aggregates,
+                         self.A.block_dim,
+                         structure=getattr(self, "r_structure", None), out=bc)
 
     def prolongate_and_apply(self, xc, x):
         es = int(self.scope.get("error_scaling") or 0)

@@ -462,12 +462,36 @@ Tensor dilu_setup(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor didx,
     return einv;
 }
 
+// strict color-split of the color-sorted slab (ro_s, ci_s): the U (upper) or
+// L part. Returns (ro_x (n+1), ci_x, map_x): offsets in slot order, columns,
+// and the full-slab position of every kept entry (the value gather map).
+std::vector<Tensor> slab_split(Tensor ro_s, Tensor ci_s, Tensor rows_sorted,
+                               Tensor colors, bool upper) {
+    check_dev(ro_s);
+    int64_t n = (int64_t)ro_s.numel() - 1;
+    TORCH_CHECK(rows_sorted.numel() == n && colors.numel() == n,
+                "slab_split: rows_sorted / colors do not have n rows");
+    hipStream_t st = cur_stream();
+    auto ro_x = torch::empty({n + 1}, ro_s.options());
+    long long nnz = amgx_hip::slab_split_count(
+        iptr(ro_s), iptr(ci_s), iptr(rows_sorted), iptr(colors), (int)n,
+        upper, iptr(ro_x), st);
+    auto ci_x = torch::empty({(int64_t)nnz}, ro_s.options());
+    auto map_x = torch::empty({(int64_t)nnz}, ro_s.options());
+    amgx_hip::slab_split_fill(iptr(ro_s), iptr(ci_s), iptr(rows_sorted),
+                              iptr(colors), (int)n, upper, iptr(ro_x),
+                              iptr(ci_x), iptr(map_x), st);
+    return {ro_x, ci_x, map_x};
+}
+
 // color-sorted DILU apply x += relax * M^{-1} rhs: matrix arrays in
 // rows_sorted order (one contiguous slab per color — reference
 // reorder-by-color layout); w, z pre-allocated scratch.
 // fused: rhs is b and the residual b - A x is folded into the forward
 // sweep (one matrix read fewer per smoother iteration than residual
 // kernel + apply); scalar and block-4 only.
+// Block matrices and small scalar levels; scalar levels past
+// SMALL_LEVEL_ROWS run dilu_split.
 void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
                  Tensor einv_s, Tensor rows_sorted,
                  std::vector<int64_t> bounds, Tensor bounds_dev, Tensor rhs,
@@ -480,7 +504,10 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
     int64_t n = (int64_t)ro_s.numel() - 1;
     // small levels: ONE fused single-WG launch for the whole apply
     // (zeroing + all colors both sweeps + relaxed axpy)
-    if (b == 1 && n <= amgx_hip::SMALL_LEVEL_ROWS) {
+    if (b == 1) {
+        TORCH_CHECK(n <= amgx_hip::SMALL_LEVEL_ROWS,
+                    "dilu_sorted: scalar levels of more than ",
+                    amgx_hip::SMALL_LEVEL_ROWS, " rows run dilu_split");
         DISPATCH(AMGX_VALUE_PAIRS, "dilu_small", (va_s, x), [&] {
             amgx_hip::dilu_small<scalar_a, scalar_v>(
                 iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
@@ -512,6 +539,59 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
         });
         amgx_hip::axpy<scalar_v>(dptr<scalar_v>(x), dptr<scalar_v>(z),
                                  (scalar_v)relax, x.numel(), st);
+    });
+}
+
+// per-color scalar DILU apply x += relax * M^{-1} rhs over the strict
+// color-split slabs; w is the one scratch vector (column-extended).
+// fused: rhs is b, the forward sweep reads the full slab (ro_f, ci_f, va_f)
+// with the residual b - A x folded in and needs w zeroed. Plain: the forward
+// sweep reads the L slab (same three arguments) and w needs no zeroing.
+// The backward sweep runs in place in w over the U slab and updates x as it
+// goes. No allocation and no host sync: capturable in a hipGraph.
+void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
+                Tensor ci_u, Tensor va_u, Tensor einv_s, Tensor rows_sorted,
+                std::vector<int64_t> bounds, Tensor rhs, Tensor w, Tensor x,
+                double relax, bool fused) {
+    int64_t n = (int64_t)ro_u.numel() - 1;
+    TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
+                    einv_s.numel() == n,
+                "dilu_split: slabs, rows_sorted and Einv disagree on n");
+    TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n,
+                "dilu_split: color bounds do not cover the n rows");
+    TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
+                "dilu_split: scalar slabs hold one value per column index");
+    TORCH_CHECK(rhs.numel() >= n && x.numel() >= n && w.numel() >= n &&
+                    (!fused || w.numel() >= x.numel()),
+                "dilu_split: vectors shorter than the matrix");
+    TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
+                    rhs.scalar_type() == x.scalar_type() &&
+                    va_u.scalar_type() == va_f.scalar_type() &&
+                    einv_s.scalar_type() == va_f.scalar_type(),
+                "dilu_split: mixed value types");
+    if (fused) w.zero_();
+    DISPATCH(AMGX_VALUE_PAIRS, "dilu_split", (va_f, x), [&] {
+        hipStream_t st = cur_stream();
+        for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
+            if (fused)
+                amgx_hip::dilu_fwd_sorted<scalar_a, scalar_v>(
+                    iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
+                    dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
+                    (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(x),
+                    dptr<scalar_v>(w), 1, st);
+            else
+                amgx_hip::dilu_fwd_lower<scalar_a, scalar_v>(
+                    iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
+                    dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
+                    (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(w), st);
+        });
+        for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
+            amgx_hip::dilu_bwd_upper<scalar_a, scalar_v>(
+                iptr(ro_u) + s, iptr(ci_u), dptr<scalar_a>(va_u),
+                dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
+                (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(x),
+                (scalar_v)relax, st);
+        });
     });
 }
 
@@ -901,6 +981,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gs_sweep_sorted", &gs_sweep_sorted);
     m.def("dilu_setup", &dilu_setup);
     m.def("dilu_sorted", &dilu_sorted);
+    m.def("dilu_split", &dilu_split);
+    m.def("slab_split", &slab_split);
     m.def("color_minmax", &color_minmax);
     m.def("size2_match", &size2_match);
     m.def("restrict_agg", &restrict_agg);

@@ -146,6 +146,19 @@ template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s);
+// Scalar per-color sweeps over the strict color-split slabs (slab_split_*):
+// plain forward w_i = Einv_i (rhs_i - sum_L a_ij w_j), no pre-zeroed w;
+// backward in place z_i = w_i - Einv_i sum_U a_ij w_j stored to w[i], with
+// x[i] += relax * z_i folded in. ro_l / ro_u / rows / einv_s pre-offset to
+// the color base.
+template <typename TA, typename TV>
+void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
+                    const TA* einv_s, const int* rows, int count,
+                    const TV* rhs, TV* w, hipStream_t s);
+template <typename TA, typename TV>
+void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
+                    const TA* einv_s, const int* rows, int count, TV* w,
+                    TV* x, TV relax, hipStream_t s);
 // Einv of the rows of one color (colors ascending)
 template <typename T>
 void dilu_setup_color(const int* ro, const int* ci, const T* va,
@@ -224,6 +237,20 @@ template <typename T>
 void agg_merge_singletons(const int* ro, const int* ci, const T* va,
                           const int* tidx, const T* diag, int n,
                           const int* agg_in, int* agg_out, hipStream_t s);
+
+// ---- strict color-split of a color-sorted slab -------------------------------
+// The U (upper) / L part of slot t keeps, in slab order, the entries with a
+// local column j < n of a later / earlier color than the row's; diagonal,
+// same-color and halo entries belong to neither. rows = rows_sorted, colors
+// per row (n entries).
+// count + scan: fills ro_x (n+1) and returns the part's nnz (one host sync)
+long long slab_split_count(const int* ro_s, const int* ci_s, const int* rows,
+                           const int* colors, int n, bool upper, int* ro_x,
+                           hipStream_t s);
+// fill: columns ci_x and map_x = position of each kept entry in the full slab
+void slab_split_fill(const int* ro_s, const int* ci_s, const int* rows,
+                     const int* colors, int n, bool upper, const int* ro_x,
+                     int* ci_x, int* map_x, hipStream_t s);
 
 // ---- SpGEMM / Galerkin -----------------------------------------------------
 // Aggregation Galerkin: COO keys agg[i]*nc+agg[j] -> radix sort ->

@@ -595,6 +595,87 @@ void transpose_csr(const int* ro, const int* ci, const T* va, int m, int n,
     dev_free(tmp, s); dev_free(perm, s); dev_free(cols, s); dev_free(rows, s);
 }
 
+// ============================================================ slab split
+// Strict color-split of a color-sorted slab: the U (upper = true) or L part
+// of the row at slot t keeps the entries with a local column j < n whose
+// color is later (U) / earlier (L) than the row's, in slab order. Diagonal,
+// same-color and halo entries belong to neither part (the comparison of
+// dilu_setup_scalar).
+template <bool UPPER>
+__device__ __forceinline__ bool slab_split_keep(int j, int n, int c,
+                                                const int* __restrict__ colors) {
+    if (j >= n) return false;
+    return UPPER ? colors[j] > c : colors[j] < c;
+}
+
+template <bool UPPER>
+__global__ __launch_bounds__(AMGX_BLOCK) void slab_split_count_kernel(
+    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
+    const int* __restrict__ rows, const int* __restrict__ colors, int n,
+    int* __restrict__ counts) {
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n) return;
+    int cnt = 0;
+    if (t < n) {
+        int c = colors[rows[t]];
+        for (int k = ro_s[t]; k < ro_s[t + 1]; ++k)
+            cnt += slab_split_keep<UPPER>(ci_s[k], n, c, colors) ? 1 : 0;
+    }
+    counts[t] = cnt;   // counts[n] = 0 closes the exclusive scan
+}
+
+template <bool UPPER>
+__global__ __launch_bounds__(AMGX_BLOCK) void slab_split_fill_kernel(
+    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
+    const int* __restrict__ rows, const int* __restrict__ colors, int n,
+    const int* __restrict__ ro_x, int* __restrict__ ci_x,
+    int* __restrict__ map_x) {
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    int c = colors[rows[t]];
+    int o = ro_x[t];
+    for (int k = ro_s[t]; k < ro_s[t + 1]; ++k) {
+        int j = ci_s[k];
+        if (slab_split_keep<UPPER>(j, n, c, colors)) {
+            ci_x[o] = j;
+            map_x[o] = k;
+            ++o;
+        }
+    }
+}
+
+long long slab_split_count(const int* ro_s, const int* ci_s, const int* rows,
+                           const int* colors, int n, bool upper, int* ro_x,
+                           hipStream_t s) {
+    auto kern = upper ? slab_split_count_kernel<true>
+                      : slab_split_count_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_1d((long long)n + 1)),
+                       dim3(AMGX_BLOCK), 0, s, ro_s, ci_s, rows, colors, n,
+                       ro_x);
+    size_t tmp_bytes = 0;
+    rocprim::exclusive_scan(nullptr, tmp_bytes, ro_x, ro_x, 0, (size_t)n + 1,
+                            rocprim::plus<int>(), s);
+    void* tmp = dev_alloc(tmp_bytes, s);
+    rocprim::exclusive_scan(tmp, tmp_bytes, ro_x, ro_x, 0, (size_t)n + 1,
+                            rocprim::plus<int>(), s);
+    int total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, ro_x + n, sizeof(int),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    dev_free(tmp, s);
+    return (long long)total;
+}
+
+void slab_split_fill(const int* ro_s, const int* ci_s, const int* rows,
+                     const int* colors, int n, bool upper, const int* ro_x,
+                     int* ci_x, int* map_x, hipStream_t s) {
+    if (n <= 0) return;
+    auto kern = upper ? slab_split_fill_kernel<true>
+                      : slab_split_fill_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_1d(n)), dim3(AMGX_BLOCK), 0, s, ro_s,
+                       ci_s, rows, colors, n, ro_x, ci_x, map_x);
+}
+
 // ============================================================ instantiation
 // aggregation setup (matching, Galerkin, ESC SpGEMM) over the value types;
 // the transpose serves classical AMG only and stays real

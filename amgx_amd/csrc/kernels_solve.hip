@@ -785,14 +785,17 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
 // per-color launches re-fetched ~num_colors scattered cache lines per
 // sweep.  ro_s/rows/einv_s pointers arrive pre-offset to the color base.
 //
-// forward: w_i = Einv_i (rhs_i - sum_{color(j)<c} A_ij w_j); w pre-zeroed so
-// the full-row product only picks up earlier colors (valid coloring => no
-// same-color off-diagonals; diagonal contributes w_i = 0).
-// FUSED folds the residual into the sweep: w_i = Einv_i (b_i - sum_k a_k
-// (x_k + w_k)).  The single gather x[j]+w[j] replaces residual kernel +
-// sweep with one matrix read, mathematically identical to r = b - A x;
-// M w = r.
-template <typename TA, typename TV, bool FUSED>
+// Scalar matrices keep, next to the full slab, its strict color-split parts
+// (slab_split_*, kernels_setup.hip): L holds the entries of earlier-color
+// local columns, U those of later colors, both in slab order, so the sums
+// below run in the order of a full-row product with the zero terms left out.
+//
+// fused forward (full slab): w_i = Einv_i (b_i - sum_k a_k (x_k + w_k)), w
+// pre-zeroed so the product only picks up earlier colors (valid coloring =>
+// no same-color off-diagonals; diagonal contributes w_i = 0).  The single
+// gather x[j]+w[j] replaces residual kernel + sweep with one matrix read,
+// mathematically identical to r = b - A x; M w = r.
+template <typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_sorted(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
     const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
@@ -801,25 +804,50 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_sorted(
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    TV sum = slab_row_dot<FUSED>(ro_s, ci_s, va_s, t, w, xres);
+    TV sum = slab_row_dot<true>(ro_s, ci_s, va_s, t, w, xres);
     w[i] = (TV)einv_s[t] * (rhs[i] - sum);
 }
 
-// backward: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j; z pre-zeroed and
-// filled color-descending, so a full-row product sees only later colors.
+// plain forward over L: w_i = Einv_i (rhs_i - sum_L A_ij w_j).  Only rows of
+// earlier colors, already written by this sweep, are read: w needs no
+// zeroing.
 template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_sorted(
-    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
-    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ wv,
-    TV* __restrict__ z) {
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_lower(
+    const int* __restrict__ ro_l, const int* __restrict__ ci_l,
+    const TA* __restrict__ va_l, const TA* __restrict__ einv_s,
+    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
+    TV* w) {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    TV sum = slab_row_dot<false>(ro_s, ci_s, va_s, t, z);
-    z[i] = wv[i] - (TV)einv_s[t] * sum;
+    TV sum = slab_row_dot<false>(ro_l, ci_l, va_l, t, w);
+    w[i] = (TV)einv_s[t] * (rhs[i] - sum);
 }
 
+// backward over U, in place, colors descending: z_i = w_i - Einv_i sum_U
+// A_ij z_j.  Later colors already hold z in w, this color still holds w, so
+// z_i overwrites w_i; the relaxed update x_i += relax z_i (the axpy
+// expression) rides along since the sweep never reads x.  The last color's
+// U rows are empty: its launch reads ro_u, w and x only.
+template <typename TA, typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_upper(
+    const int* __restrict__ ro_u, const int* __restrict__ ci_u,
+    const TA* __restrict__ va_u, const TA* __restrict__ einv_s,
+    const int* __restrict__ rows, int count, TV* w, TV* __restrict__ x,
+    TV relax) {
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    int i = rows[t];
+    TV sum = slab_row_dot<false>(ro_u, ci_u, va_u, t, w);
+    TV z = w[i] - (TV)einv_s[t] * sum;
+    w[i] = z;
+    x[i] += relax * z;
+}
+
+// block forward: w_i = Einv_i (rhs_i - sum_{color(j)<c} A_ij w_j); w
+// pre-zeroed so the full-row product only picks up earlier colors.
+// block backward: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j; z pre-zeroed
+// and filled color-descending, so a full-row product sees only later colors.
 template <typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_block_sorted(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
@@ -935,7 +963,8 @@ void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
 }
 
 // xres != nullptr selects the fused-residual sweep (rhs = b, xres = x);
-// there is no fused kernel for generic block sizes (caller guards)
+// there is no fused kernel for generic block sizes, and the plain scalar
+// sweep runs over the L slab (dilu_fwd_lower) instead (caller guards both)
 template <typename TA, typename TV>
 void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
@@ -943,11 +972,13 @@ void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      hipStream_t s) {
     if (count <= 0) return;
     if (b == 1) {
-        auto kern = xres ? dilu_fwd_scalar_sorted<TA, TV, true>
-                         : dilu_fwd_scalar_sorted<TA, TV, false>;
-        hipLaunchKernelGGL(kern, dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0,
-                           s, ro_s, ci_s, va_s, einv_s, rows, count, rhs,
-                           xres, w);
+        if (!xres)
+            throw std::runtime_error(
+                "dilu_fwd_sorted: the plain scalar sweep is dilu_fwd_lower");
+        hipLaunchKernelGGL((dilu_fwd_scalar_sorted<TA, TV>),
+                           dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
+                           ro_s, ci_s, va_s, einv_s, rows, count, rhs, xres,
+                           w);
     } else if constexpr (is_cplx<TV>::value) {
         throw std::runtime_error(
             "dilu_fwd_sorted: complex block matrices are unsupported");
@@ -961,15 +992,15 @@ void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
     }
 }
 
+// block matrices only; the scalar backward sweep is dilu_bwd_upper
 template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s) {
     if (count <= 0) return;
     if (b == 1) {
-        hipLaunchKernelGGL((dilu_bwd_scalar_sorted<TA, TV>),
-                           dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
-                           ro_s, ci_s, va_s, einv_s, rows, count, wv, z);
+        throw std::runtime_error(
+            "dilu_bwd_sorted: the scalar sweep is dilu_bwd_upper");
     } else if constexpr (is_cplx<TV>::value) {
         throw std::runtime_error(
             "dilu_bwd_sorted: complex block matrices are unsupported");
@@ -981,6 +1012,26 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                            dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
                            ro_s, ci_s, va_s, einv_s, rows, count, wv, z, b);
     }
+}
+
+template <typename TA, typename TV>
+void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
+                    const TA* einv_s, const int* rows, int count,
+                    const TV* rhs, TV* w, hipStream_t s) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL((dilu_fwd_scalar_lower<TA, TV>), dim3(grid_1d(count)),
+                       dim3(AMGX_BLOCK), 0, s, ro_l, ci_l, va_l, einv_s, rows,
+                       count, rhs, w);
+}
+
+template <typename TA, typename TV>
+void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
+                    const TA* einv_s, const int* rows, int count, TV* w,
+                    TV* x, TV relax, hipStream_t s) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL((dilu_bwd_scalar_upper<TA, TV>), dim3(grid_1d(count)),
+                       dim3(AMGX_BLOCK), 0, s, ro_u, ci_u, va_u, einv_s, rows,
+                       count, w, x, relax);
 }
 
 // ============================================================ transfers
@@ -1130,6 +1181,8 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
     AMGX_INSTANTIATE(dilu_small, TA, TV)                                        \
     AMGX_INSTANTIATE(dilu_fwd_sorted, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_bwd_sorted, TA, TV)                                   \
+    AMGX_INSTANTIATE(dilu_fwd_lower, TA, TV)                                    \
+    AMGX_INSTANTIATE(dilu_bwd_upper, TA, TV)                                    \
     AMGX_INSTANTIATE(gs_sweep_small, TA, TV)                                    \
     AMGX_INSTANTIATE(gs_rows_sorted, TA, TV)                                    \
     AMGX_INSTANTIATE(gs_smooth_rows, TA, TV)                                    \

@@ -186,12 +186,13 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
 
 
 def restrict_agg(r, aggregates, num_aggregates, block_dim: int = 1,
-                 structure=None):
+                 structure=None, out=None):
     """rc[I] = sum_{i in I} r[i] (reference restrictResidualKernel,
     src/aggregation/aggregation_amg_level.cu:93-180). ``structure`` =
-    (offsets, fine_ids) aggregate-CSR for the deterministic no-atomics path."""
+    (offsets, fine_ids) aggregate-CSR for the deterministic no-atomics path.
+    ``out``: write into the prefix of this vector instead of a fresh one."""
     return _backend(r).restrict_agg(r, aggregates, num_aggregates, block_dim,
-                                    structure)
+                                    structure, out)
 
 
 def prolongate_agg(x, xc, aggregates, block_dim: int = 1):

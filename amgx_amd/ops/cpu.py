@@ -425,16 +425,21 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
 
 
 def restrict_agg(r, aggregates, num_aggregates, block_dim: int = 1,
-                 structure=None):
+                 structure=None, out=None):
     agg = aggregates.to(torch.int64)
     r = r.reshape(-1)[:agg.numel() * block_dim]   # owned prefix (distributed)
-    rc = torch.zeros(num_aggregates * block_dim, dtype=r.dtype)
+    if out is not None and out.dtype == r.dtype:
+        rc = out.reshape(-1)[:num_aggregates * block_dim].zero_()
+    else:
+        rc = torch.zeros(num_aggregates * block_dim, dtype=r.dtype)
     if block_dim == 1:
         rc.index_add_(0, agg, r.reshape(-1))
     else:
         idx = (agg[:, None] * block_dim +
                torch.arange(block_dim, dtype=torch.int64)[None, :]).reshape(-1)
         rc.index_add_(0, idx, r.reshape(-1))
+    if out is not None and out.dtype != r.dtype:
+        out.reshape(-1)[:rc.numel()].copy_(rc)
     return rc
 
 

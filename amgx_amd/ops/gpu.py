@@ -220,9 +220,12 @@ class _Slabs:
     (reference reorder-by-color, include/matrix.h:766): slot-ordered row
     offsets ro_s, gathered columns ci_s, the nz gather map nzmap (for value
     re-gathers after replace_coefficients), perm = rows_sorted as int64 and
-    its inverse slot_of_row; copies holds the gathered value arrays."""
+    its inverse slot_of_row; copies holds the gathered value arrays.
+    upper / lower: the strict color-split parts of the slab for the scalar
+    DILU sweeps, each (offsets, columns, int32 map into the full slab), built
+    on first use by _slab_part."""
     __slots__ = ("coloring", "ro_s", "ci_s", "nzmap", "perm", "slot_of_row",
-                 "copies")
+                 "copies", "upper", "lower")
 
 
 def _slabs(A, coloring):
@@ -233,6 +236,7 @@ def _slabs(A, coloring):
         st = _Slabs()
         st.coloring = coloring
         st.copies = {}
+        st.upper = st.lower = None
         n = A.n_rows
         perm = coloring.rows_sorted.to(torch.int64)
         ro64 = A.row_offsets.to(torch.int64)
@@ -265,15 +269,39 @@ def _slab_copy(st, name, src, gather):
     return hit[1]
 
 
+def _slab_part(st, upper):
+    """Structure (ro, ci, map) of the U (upper) or L part of the slab: the
+    entries of later- / earlier-color local columns, in slab order."""
+    part = st.upper if upper else st.lower
+    if part is None:
+        part = tuple(_core.slab_split(st.ro_s, st.ci_s,
+                                      st.coloring.rows_sorted,
+                                      st.coloring.colors, bool(upper)))
+        if upper:
+            st.upper = part
+        else:
+            st.lower = part
+    return part
+
+
+def _split_path(A):
+    """Scalar levels past the single-workgroup size sweep the split slabs."""
+    return A.block_dim == 1 and A.n_rows > _core.SMALL_LEVEL_ROWS
+
+
 class DiluState:
     """Device DILU factor state: Einv in original row order (einv) plus the
-    color-sorted matrix/Einv copies the sweeps read contiguously."""
-    __slots__ = ("einv", "va_s", "einv_s")
+    color-sorted matrix/Einv copies the sweeps read contiguously. On the
+    split-slab path va_u holds the values of the U part and va_l, gathered
+    on the first plain apply, those of the L part."""
+    __slots__ = ("einv", "va_s", "einv_s", "va_u", "va_l")
 
-    def __init__(self, einv, va_s, einv_s):
+    def __init__(self, einv, va_s, einv_s, va_u=None):
         self.einv = einv
         self.va_s = va_s
         self.einv_s = einv_s
+        self.va_u = va_u
+        self.va_l = None
 
     def cpu(self):          # test convenience: compare against host Einv
         return self.einv.cpu()
@@ -311,14 +339,36 @@ def dilu_setup(A, coloring):
     va_s = A.values.reshape(A.nnz, -1)[st.nzmap].reshape(-1).contiguous()
     einv_s = einv.reshape(A.n_rows, bb)[st.perm].reshape(-1).contiguous() \
         if A.block_dim > 1 else einv[st.perm].contiguous()
-    return DiluState(einv, va_s, einv_s)
+    va_u = _gather_part(va_s, _slab_part(st, True)) if _split_path(A) \
+        else None
+    return DiluState(einv, va_s, einv_s, va_u)
+
+
+def _gather_part(va_s, part):
+    out = torch.empty(part[2].numel(), dtype=va_s.dtype, device=va_s.device)
+    _core.gather(va_s, part[2], 1, out)
+    return out
 
 
 def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused):
     n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
     w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
-    z = _scratch(A, "dilu_z", n, x.dtype)
     st = _slabs(A, coloring)
+    if _split_path(A):
+        ro_u, ci_u, _ = _slab_part(st, True)
+        if fused:
+            fwd = (st.ro_s, st.ci_s, Einv.va_s)
+        else:
+            ro_l, ci_l, _ = part = _slab_part(st, False)
+            if Einv.va_l is None:
+                Einv.va_l = _gather_part(Einv.va_s, part)
+            fwd = (ro_l, ci_l, Einv.va_l)
+        _core.dilu_split(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
+                         coloring.rows_sorted, coloring.bounds,
+                         rhs.reshape(-1), w, x.reshape(-1),
+                         float(relaxation), fused)
+        return
+    z = _scratch(A, "dilu_z", n, x.dtype)
     _core.dilu_sorted(st.ro_s, st.ci_s, Einv.va_s, A.block_dim, Einv.einv_s,
                       coloring.rows_sorted, coloring.bounds,
                       coloring.bounds_dev, rhs.reshape(-1), w, z,
@@ -421,14 +471,21 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
 
 
 def restrict_agg(r, aggregates, num_aggregates, block_dim: int = 1,
-                 structure=None):
-    rc = torch.empty(num_aggregates * block_dim, dtype=r.dtype,
-                     device=r.device)
+                 structure=None, out=None):
+    """``out``: a vector of at least num_aggregates * block_dim entries whose
+    prefix receives the result (no allocation, no copy)."""
+    nc = num_aggregates * block_dim
+    if out is None or out.dtype != r.dtype:
+        rc = torch.empty(nc, dtype=r.dtype, device=r.device)
+    else:
+        rc = out.reshape(-1)[:nc]
     if structure is not None:
         off, fids = structure
         _core.restrict_csr(r.reshape(-1), off, fids, block_dim, rc)
     else:
         _core.restrict_agg(r.reshape(-1), aggregates, block_dim, rc)
+    if out is not None and out.dtype != r.dtype:
+        out.reshape(-1)[:nc].copy_(rc)
     return rc
 
 

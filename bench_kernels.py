@@ -93,9 +93,28 @@ def main():
         lambda: ops.gs_sweep(A, dinv, b, x.clone(), col, 0.9),
         max(args.iters // 4, 2), sync), spmv_bytes + n * 24)
     einv = dilu_setup(A, col)
-    rec("dilu_apply", bench(
-        lambda: dilu_solve(A, einv, col, r, 0.75, y), args.iters, sync),
-        2 * rows_bytes + n * 40)
+    B = ops._backend(A)
+    t_apply = bench(lambda: dilu_solve(A, einv, col, r, 0.75, y), args.iters,
+                    sync)
+    # bytes of one scalar DILU apply, every array counted once per sweep.
+    # Both sweeps read offsets + rows_sorted + Einv (n * 16 + 4); the
+    # backward sweep reads the U part, reads and writes w and x (n * 32).
+    # dilu_apply: forward over the L part, reads r and w, writes w (n * 24).
+    # dilu_smooth: w memset (n * 8), forward over the full slab, reads b, x
+    # and w, writes w (n * 32).
+    st = A._cache.get("slabs")
+    if st is not None and getattr(st, "upper", None) is not None:
+        nnz_u = st.upper[1].numel()
+        nnz_l = st.lower[1].numel() if st.lower is not None else nnz - n - nnz_u
+    else:                       # symmetric pattern: half the off-diagonals
+        nnz_u = nnz_l = (nnz - n) // 2
+    sweep_bytes = n * 16 + 4
+    bwd_bytes = nnz_u * 12 + sweep_bytes + n * 32
+    rec("dilu_apply", t_apply, nnz_l * 12 + sweep_bytes + n * 24 + bwd_bytes)
+    if getattr(B, "dilu_smooth", None) is not None:
+        rec("dilu_smooth", bench(
+            lambda: B.dilu_smooth(A, einv, col, b, y, 0.75), args.iters,
+            sync), n * 8 + nnz * 12 + sweep_bytes + n * 32 + bwd_bytes)
 
     # block-4 kernels: MFMA wave path vs the scalar baseline
     from amgx_amd.problems import block_laplacian
