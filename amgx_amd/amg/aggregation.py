@@ -3,8 +3,11 @@ size2/size4/size8, multi_pairwise, parallel_greedy, serial_greedy, geo,
 dummy; registered src/core.cu:560-690).
 
 Each selector returns (aggregates int32[n_rows], num_aggregates). SIZE_2 is
-the gfx950-kernel handshaking matching (ops.size2_matching); SIZE_4/8 and
-MULTI_PAIRWISE compose repeated pairwise passes like the reference.
+the gfx950-kernel handshaking matching (ops.size2_matching); SIZE_4/8
+compose repeated pairwise passes like the reference. MULTI_PAIRWISE on a
+device matrix is the capped handshake matching on a weight graph
+(multi_pairwise_passes over ops.pairwise_weights / ops.pairwise_matching);
+on a host matrix it is a sequential greedy matcher.
 """
 
 from __future__ import annotations
@@ -72,11 +75,81 @@ def select_parallel_greedy(A, scope):
     return _compose_passes(A, scope, 1)
 
 
+def _multi_pairwise_pass_count(scope) -> int:
+    override = int(scope.get("aggregation_passes") or 0)
+    if override > 0:
+        return override
+    size = int(scope.get("aggregate_size") or 4)
+    return max(1, int(np.ceil(np.log2(max(size, 2)))))
+
+
+def multi_pairwise_passes(A, scope, return_levels: bool = False):
+    """The MULTI_PAIRWISE pass loop (reference multi_pairwise.cu
+    setAggregates), written against ``ops`` so that it runs on host and
+    device matrices alike: edge weights once, then per pass a handshake
+    matching (ops.pairwise_matching) on the weight graph, coarsened between
+    passes by the aggregation Galerkin product.
+
+    ``full_ghost_level`` = 0: the next graph is the Galerkin product of the
+    weight matrix (A's structure, w as values); its off-diagonal values are
+    the next weights, its diagonal is ignored. 1: the Galerkin product of A
+    itself, weights recomputed from it by the formula.
+    ``merge_singletons`` = 2 caps aggregates at 2^passes + passes - passes/2
+    rows (3, 5, 10, 18 for 1-4 passes); other modes have no cap.
+
+    Returns (aggregates int32 (n,), num); with ``return_levels`` also the
+    list of per-pass (level_agg, num, sizes, rounds)."""
+    from ..matrix import CSRMatrix
+    passes = _multi_pairwise_pass_count(scope)
+    merge = int(scope.get("merge_singletons"))
+    formula = int(scope.get("weight_formula"))
+    full_ghost = int(scope.get("full_ghost_level"))
+    maxit = int(scope.get("max_matching_iterations"))
+    max_un = float(scope.get("max_unassigned_percentage"))
+    min_rows = int(scope.get("min_coarse_rows"))
+    cap = 2 ** passes + passes - passes // 2 if merge == 2 else 0
+
+    n = A.n_rows
+    w = ops.pairwise_weights(A, formula)
+    dev = w.device
+    ro, ci, work = A.row_offsets, A.col_indices, A
+    sizes = torch.ones(n, dtype=torch.int32, device=dev)
+    agg, num, levels = None, n, []
+    for p in range(passes):
+        level_agg, num, sizes, rounds = ops.pairwise_matching(
+            ro, ci, w, n, sizes, cap, merge, maxit, max_un, p)
+        levels.append((level_agg, num, sizes, rounds))
+        agg = level_agg if agg is None else level_agg[agg.long()]
+        if p == passes - 1 or num <= min_rows or num <= 1 or num == n:
+            break
+        # ghost level: the graph of the next pass
+        if work.n_cols != work.n_rows:
+            raise NotImplementedError(
+                "MULTI_PAIRWISE ghost levels need a view without halo "
+                "columns")
+        if full_ghost:
+            work = ops.galerkin_aggregation(work, level_agg, num)
+            w = ops.pairwise_weights(work, formula)
+        else:
+            work = ops.galerkin_aggregation(
+                CSRMatrix(ro, ci, w, n_cols=n), level_agg, num)
+            w = work.values
+        ro, ci, n = work.row_offsets, work.col_indices, num
+    if return_levels:
+        return agg, num, levels
+    return agg, num
+
+
 @register_agg_selector("MULTI_PAIRWISE")
 def select_multi_pairwise(A, scope):
     """Notay-style multiple pairwise aggregation (reference
-    multi_pairwise.cu): sequential greedy matching over edges sorted by
-    descending scaled strength, composed log2(aggregate_size) times."""
+    multi_pairwise.cu). A device matrix runs the parallel handshake matching
+    of ``multi_pairwise_passes`` on gfx950 kernels. A host matrix, and a
+    device matrix with ``serial_matching`` = 1, runs the sequential greedy
+    matcher below: edges sorted by descending scaled strength, composed
+    log2(aggregate_size) times (the reference's serial_matching)."""
+    if A.is_cuda and not int(scope.get("serial_matching") or 0):
+        return multi_pairwise_passes(A, scope)
     size = int(scope.get("aggregate_size") or 4)
     passes = max(1, int(np.ceil(np.log2(max(size, 2)))))
 

@@ -106,7 +106,18 @@ def _register_core_parameters() -> None:
     P("max_unassigned_percentage", float, 0.05, "allowed unaggregated fraction")
     P("coarseAgenerator", str, "LOW_DEG", "aggregation Galerkin generator",
       ("LOW_DEG", "THRUST", "HYBRID"))
-    P("full_ghost_level", int, 0, "distributed aggregation ghost-level mode")
+    P("full_ghost_level", int, 0,
+      "MULTI_PAIRWISE graph between passes: 0 = Galerkin product of the "
+      "edge weights, 1 = Galerkin product of A with weights recomputed")
+    P("weight_formula", int, 0,
+      "MULTI_PAIRWISE edge weight: 0 = 0.5(|a_ij|+|a_ji|)/max(|a_ii|,|a_jj|), "
+      "1 = -0.5(a_ij/a_ii + a_ji/a_jj) (scalar real matrices)")
+    P("merge_singletons", int, 1,
+      "MULTI_PAIRWISE leftovers: 0 = singletons, 1 = join the strongest "
+      "aggregated neighbour, 2 = join under the aggregate size cap")
+    P("serial_matching", int, 0,
+      "MULTI_PAIRWISE: 1 = sequential greedy matcher on the host also for a "
+      "device matrix (host matrices always use it)")
     # --- classical --------------------------------------------------------------------
     P("strength", str, "AHAT", "strength-of-connection metric", ("AHAT", "ALL", "AFFINITY"))
     P("strength_threshold", float, 0.25, "classical strength threshold")
@@ -189,15 +200,12 @@ def _register_core_parameters() -> None:
     # exchange replaces the comm knobs.
     for name, typ, dflt, doc in (
         ("aggregation_edge_weight_component", int, 0, "block weight component"),
-        ("weight_formula", int, 0, "pairwise matching weight formula"),
         ("notay_weights", int, 0, "Notay quality weights in matching"),
         ("filter_weights", int, 0, "filter small matching weights"),
         ("filter_weights_alpha", float, 0.25, "weight filter threshold"),
-        ("serial_matching", int, 0, "serial matching fallback"),
         ("handshaking_phases", int, 1, "matching handshake phases"),
         ("modified_handshake", int, 0, "modified handshaking"),
         ("late_rejection", int, 0, "late rejection in matching"),
-        ("merge_singletons", int, 1, "merge unmatched rows into aggregates"),
         ("weakness_bound", float, 0.0, "weak-edge bound in matching"),
         ("ghost_offdiag_limit", int, 0, "ghost off-diagonal limit"),
         ("coarse_smoother", str, "NOSOLVER", "smoother on coarse levels"),

@@ -2,14 +2,16 @@
 //
 // Besides 1:1 kernel wrappers this TU hosts the C++-side orchestration loops
 // whose per-step launches would otherwise pay a Python round trip per color /
-// per round: the whole DILU apply, the MIN_MAX coloring loop and the SIZE_2
-// matching loop each run as ONE call from Python.
+// per round: the whole DILU apply, the MIN_MAX coloring loop, the SIZE_2
+// matching loop and one MULTI_PAIRWISE pass each run as ONE call from Python.
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <pybind11/complex.h>
 
+#include <algorithm>
 #include <array>
+#include <climits>
 #include <complex>
 #include <vector>
 
@@ -652,6 +654,138 @@ Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
     return agg;   // root fine-node ids; Python renumbers with torch.unique
 }
 
+// MULTI_PAIRWISE edge weights, one double per stored entry
+Tensor pairwise_weights(Tensor ro, Tensor ci, Tensor va, Tensor tidx,
+                        Tensor diag, int64_t n, int64_t formula) {
+    check_dev(va);
+    TORCH_CHECK(formula == 0 || formula == 1,
+                "pairwise_weights: weight_formula must be 0 or 1");
+    TORCH_CHECK_NOT_IMPLEMENTED(formula == 0 || !va.is_complex(),
+                                "pairwise_weights: weight_formula 1 is "
+                                "signed and unavailable for complex values");
+    TORCH_CHECK(tidx.numel() == ci.numel() && va.numel() == ci.numel() &&
+                    diag.numel() == n && ro.numel() == n + 1,
+                "pairwise_weights: array sizes do not match the structure");
+    auto w = torch::empty({ci.numel()}, va.options().dtype(torch::kFloat64));
+    DISPATCH(AMGX_VALUE_TYPES, "pairwise_weights", (va), [&] {
+        amgx_hip::pairwise_weights<scalar_t>(
+            iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
+            dptr<scalar_t>(diag), (int)n, (int)formula, dptr<double>(w),
+            cur_stream());
+    });
+    return w;
+}
+
+// lanes per row of the propose kernel: thread-per-row up to 8 entries per
+// row on average, 8 lanes above. Measured on MI355X (profiles/NOTES.md):
+// thread-per-row wins at 7.0 entries per row, 8 lanes from 10.2 upwards.
+int pairwise_lanes(int64_t nnz, int64_t n) {
+    double avg = (double)nnz / (double)std::max<int64_t>(n, 1);
+    return avg <= 8.0 ? 1 : 8;
+}
+
+// one propose step (tests and bench_kernels.py); lanes = 0 routes by degree
+Tensor pairwise_propose(Tensor ro, Tensor ci, Tensor w, int64_t n, Tensor agg,
+                        Tensor sizes, int64_t cap, int64_t seed,
+                        int64_t lanes) {
+    check_dev(w);
+    TORCH_CHECK(ro.numel() == n + 1 && w.numel() == ci.numel() &&
+                    agg.numel() == n && sizes.numel() == n,
+                "pairwise_propose: array sizes do not match the structure");
+    auto prop = torch::empty({n}, ro.options().dtype(torch::kInt32));
+    int icap = cap <= 0 ? INT_MAX : (int)std::min<int64_t>(cap, INT_MAX);
+    if (lanes == 0) lanes = pairwise_lanes(ci.numel(), n);
+    amgx_hip::pairwise_propose(iptr(ro), iptr(ci), dptr<double>(w), (int)n,
+                               iptr(agg), iptr(sizes), icap, (int)seed,
+                               (int)lanes, iptr(prop), cur_stream());
+    return prop;
+}
+
+// Handshake rounds + leftover phase + renumbering of one MULTI_PAIRWISE pass
+// in one call: (agg int32[n], num, sizes int32[num], rounds). One integer
+// read-back per round, as size2_match. cap <= 0 = unbounded.
+std::tuple<Tensor, int64_t, Tensor, int64_t> pairwise_match(
+    Tensor ro, Tensor ci, Tensor w, int64_t n, Tensor sizes_in, int64_t cap,
+    int64_t merge_singletons, int64_t max_iters, double max_unassigned,
+    int64_t seed, int64_t lanes) {
+    check_dev(w);
+    TORCH_CHECK(ro.numel() == n + 1 && w.numel() == ci.numel() &&
+                    sizes_in.numel() == n,
+                "pairwise_match: array sizes do not match the structure");
+    TORCH_CHECK(merge_singletons >= 0 && merge_singletons <= 2,
+                "pairwise_match: merge_singletons must be 0, 1 or 2");
+    auto iopt = ro.options().dtype(torch::kInt32);
+    auto agg = torch::full({n}, -1, iopt);
+    auto sizes = sizes_in.clone();
+    if (n == 0) return {agg, 0, sizes, 0};
+    auto prop = torch::empty({n}, iopt);
+    auto counter = torch::zeros({1}, iopt);
+    hipStream_t st = cur_stream();
+    const int* rp = iptr(ro);
+    const int* cp = iptr(ci);
+    const double* wp = dptr<double>(w);
+    int icap = cap <= 0 ? INT_MAX : (int)std::min<int64_t>(cap, INT_MAX);
+    if (lanes == 0) lanes = pairwise_lanes(ci.numel(), n);
+    auto unaggregated = [&] {
+        counter.zero_();
+        amgx_hip::pairwise_count_unaggregated(iptr(agg), (int)n,
+                                              iptr(counter), st);
+        return (int64_t)counter.cpu().item<int>();
+    };
+
+    int64_t un = n, rounds = 0;
+    while (rounds < max_iters && un > 0 &&
+           !((double)un < max_unassigned * (double)n)) {
+        amgx_hip::pairwise_propose(rp, cp, wp, (int)n, iptr(agg), iptr(sizes),
+                                   icap, (int)seed, (int)lanes, iptr(prop),
+                                   st);
+        amgx_hip::pairwise_match(iptr(prop), (int)n, iptr(agg), iptr(sizes),
+                                 st);
+        ++rounds;
+        int64_t left = unaggregated();
+        if (left == un) break;   // no pair formed
+        un = left;
+    }
+
+    if (merge_singletons == 1 && un > 0) {
+        auto agg_next = torch::empty_like(agg);
+        while (un > 0) {
+            amgx_hip::pairwise_join_sweep(rp, cp, wp, (int)n, iptr(agg),
+                                          (int)seed, iptr(agg_next), st);
+            std::swap(agg, agg_next);
+            int64_t left = unaggregated();
+            if (left == un) break;   // the sweep changed nothing
+            un = left;
+        }
+    } else if (merge_singletons == 2 && un > 0) {
+        auto bid_root = torch::empty({n}, iopt);
+        auto bid_w = torch::zeros({n}, ro.options().dtype(torch::kInt64));
+        auto bid_i = torch::full({n}, n, iopt);
+        while (un > 0) {
+            amgx_hip::pairwise_join_capped(
+                rp, cp, wp, (int)n, iptr(agg), iptr(sizes), icap, (int)seed,
+                iptr(bid_root),
+                reinterpret_cast<unsigned long long*>(dptr<int64_t>(bid_w)),
+                iptr(bid_i), st);
+            int64_t left = unaggregated();
+            if (left == un) break;   // no proposal was made
+            un = left;
+        }
+    }
+
+    auto ids = torch::empty({n + 1}, iopt);
+    size_t tmp_bytes = amgx_hip::pairwise_renumber_tmp_bytes((int)n);
+    auto tmp = torch::empty({(int64_t)std::max<size_t>(tmp_bytes, 16)},
+                            ro.options().dtype(torch::kUInt8));
+    auto agg_out = torch::empty({n}, iopt);
+    auto sizes_out = torch::zeros({n}, iopt);
+    amgx_hip::pairwise_renumber(iptr(agg), (int)n, iptr(sizes_in), iptr(ids),
+                                tmp.data_ptr(), tmp_bytes, iptr(agg_out),
+                                iptr(sizes_out), st);
+    int64_t num = ids[n].cpu().item<int>();
+    return {agg_out, num, sizes_out.narrow(0, 0, num).clone(), rounds};
+}
+
 // ---------------------------------------------------------------- transfers
 void restrict_agg(Tensor r, Tensor agg, int64_t b, Tensor rc) {
     rc.zero_();
@@ -985,6 +1119,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("slab_split", &slab_split);
     m.def("color_minmax", &color_minmax);
     m.def("size2_match", &size2_match);
+    m.def("pairwise_weights", &pairwise_weights);
+    m.def("pairwise_propose", &pairwise_propose);
+    m.def("pairwise_match", &pairwise_match);
     m.def("restrict_agg", &restrict_agg);
     m.def("restrict_csr", &restrict_csr);
     m.def("prolongate_agg", &prolongate_agg);

@@ -238,6 +238,47 @@ void agg_merge_singletons(const int* ro, const int* ci, const T* va,
                           const int* tidx, const T* diag, int n,
                           const int* agg_in, int* agg_out, hipStream_t s);
 
+// ---- MULTI_PAIRWISE ----------------------------------------------------------
+// Matching on a weight graph w[nnz] over the structure (ro, ci) of n rows;
+// entries with w > 0 are edges, compared by (w, hash of the pair, lo, hi).
+// State: agg[i] = root row of i's aggregate or -1, sizes[i] = size of a
+// root's aggregate or of an unaggregated row. No launcher allocates or
+// synchronizes; scratch comes from the caller.
+// pairwise_weights: [value]; formula 0 = 0.5(|a_ij|+|a_ji|)/max(|a_ii|,|a_jj|)
+// (complex: moduli in double), 1 = -0.5(a_ij/a_ii + a_ji/a_jj) (real only)
+template <typename T>
+void pairwise_weights(const int* ro, const int* ci, const T* va,
+                      const int* tidx, const T* diag, int n, int formula,
+                      double* w, hipStream_t s);
+// lanes per row: 1 or 8; both write the same prop
+void pairwise_propose(const int* ro, const int* ci, const double* w, int n,
+                      const int* agg, const int* sizes, int cap, int seed,
+                      int lanes, int* prop, hipStream_t s);
+void pairwise_match(const int* prop, int n, int* agg, int* sizes,
+                    hipStream_t s);
+// *count += number of rows with agg < 0
+void pairwise_count_unaggregated(const int* agg, int n, int* count,
+                                 hipStream_t s);
+// merge_singletons = 1: one double-buffered sweep agg_in -> agg_out
+void pairwise_join_sweep(const int* ro, const int* ci, const double* w, int n,
+                         const int* agg_in, int seed, int* agg_out,
+                         hipStream_t s);
+// merge_singletons = 2: one capped round (bid, tie-break, accept). bid_root
+// (n) is scratch; bid_w (n) must be 0 and bid_i (n) must be n on entry and
+// are left so.
+void pairwise_join_capped(const int* ro, const int* ci, const double* w, int n,
+                          int* agg, int* sizes, int cap, int seed,
+                          int* bid_root, unsigned long long* bid_w, int* bid_i,
+                          hipStream_t s);
+// Roots (agg[i] == i, rows still at -1 included) get consecutive ids in
+// ascending order: agg_out[i] = id of i's root, sizes_out[id] (zeroed by the
+// caller) = sum of sizes_in over the members. ids: n + 1 ints of scratch,
+// ids[n] = number of aggregates afterwards; tmp: pairwise_renumber_tmp_bytes.
+size_t pairwise_renumber_tmp_bytes(int n);
+void pairwise_renumber(int* agg, int n, const int* sizes_in, int* ids,
+                       void* tmp, size_t tmp_bytes, int* agg_out,
+                       int* sizes_out, hipStream_t s);
+
 // ---- strict color-split of a color-sorted slab -------------------------------
 // The U (upper) / L part of slot t keeps, in slab order, the entries with a
 // local column j < n of a later / earlier color than the row's; diagonal,

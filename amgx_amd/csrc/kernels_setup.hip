@@ -1,8 +1,10 @@
 // Setup-path kernels: MIN_MAX coloring rounds, SIZE_2 pairwise-matching
-// aggregation, sort-based Galerkin products / SpGEMM / transpose.
+// aggregation, MULTI_PAIRWISE weights / matching / renumbering, sort-based
+// Galerkin products / SpGEMM / transpose.
 //
 // Reference behaviors: src/matrix_coloring/min_max.cu,
 // src/aggregation/selectors/size2_selector.cu,
+// src/aggregation/selectors/multi_pairwise.cu,
 // src/aggregation/coarseAgenerators/thrust_coarse_A_generator.cu (the
 // sort/reduce_by_key Galerkin), src/csr_multiply_detail.cu (SpGEMM; here an
 // ESC expand-sort-compress scheme on rocPRIM radix sort — the LDS-hash
@@ -209,6 +211,386 @@ void agg_merge_singletons(const int* ro, const int* ci, const T* va,
     hipLaunchKernelGGL((agg_singleton_kernel<T>), dim3(grid_1d(n)),
                        dim3(AMGX_BLOCK), 0, s, ro, ci, va, tidx, diag, n,
                        agg_in, agg_out);
+}
+
+// ============================================================ MULTI_PAIRWISE
+// Pairwise handshake matching on a precomputed weight graph w[nnz]
+// (reference src/aggregation/selectors/multi_pairwise.cu). The matching
+// kernels read w, never matrix values: the graph of a later pass is the
+// Galerkin product of the weights and has no matrix behind it. Everything is
+// deterministic: candidate edges are compared by the total order
+// (w, h(lo, hi), lo, hi) on unordered pairs {lo, hi}, and the only atomics
+// are integer max / min / add, whose result does not depend on arrival order.
+
+// w_k for entry k = (i, j); 0 for the diagonal, a halo column, a missing
+// transpose entry or a zero divisor. The operand order makes w_ij == w_ji
+// bitwise: both sums are commutative. Contraction stays off so the value is
+// the one the per-row host oracle computes.
+template <typename T>
+__device__ __forceinline__ double pairwise_weight(const T* __restrict__ va,
+                                                  const int* __restrict__ tidx,
+                                                  const T* __restrict__ diag,
+                                                  int k, int i, int j, int n,
+                                                  int formula) {
+#pragma clang fp contract(off)
+    if (j == i || j >= n) return 0.0;
+    int t = tidx[k];
+    if (t < 0) return 0.0;
+    if (formula == 0) {
+        double di = absd(diag[i]), dj = absd(diag[j]);
+        double m = di > dj ? di : dj;
+        if (!(m > 0.0)) return 0.0;
+        return 0.5 * (absd(va[k]) + absd(va[t])) / m;
+    }
+    if constexpr (is_cplx<T>::value) {
+        return 0.0;   // formula 1 is signed: rejected for complex by the caller
+    } else {
+        double di = (double)diag[i], dj = (double)diag[j];
+        if (di == 0.0 || dj == 0.0) return 0.0;
+        return -0.5 * ((double)va[k] / di + (double)va[t] / dj);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_weights_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const T* __restrict__ va, const int* __restrict__ tidx,
+    const T* __restrict__ diag, int n, int formula, double* __restrict__ w) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int k = ro[i]; k < ro[i + 1]; ++k)
+        w[k] = pairwise_weight(va, tidx, diag, k, i, ci[k], n, formula);
+}
+
+// 32-bit hash of the unordered pair {i, j}
+__device__ __forceinline__ unsigned int pair_hash(int i, int j,
+                                                  unsigned int seed) {
+    unsigned int lo = (unsigned)min(i, j), hi = (unsigned)max(i, j);
+    return hash_u32(hash_u32(lo, seed) ^ hi, seed);
+}
+
+// A row's candidate: the other end j of an edge (-1 = none), its weight and
+// pair hash. cand_better(i, a, b): edge {i, a.j} is larger than {i, b.j}.
+struct PairCand {
+    double w;
+    unsigned int h;
+    int j;
+};
+
+__device__ __forceinline__ bool cand_better(int i, const PairCand& a,
+                                            const PairCand& b) {
+    if (a.j < 0) return false;
+    if (b.j < 0) return true;
+    if (a.w != b.w) return a.w > b.w;
+    if (a.h != b.h) return a.h > b.h;
+    int alo = min(i, a.j), blo = min(i, b.j);
+    if (alo != blo) return alo > blo;
+    return max(i, a.j) > max(i, b.j);
+}
+
+// Entry k of row i as a matching candidate: an edge (w > 0) to another local
+// row that is unaggregated and fits under the cap together with i.
+__device__ __forceinline__ PairCand match_cand(
+    const int* __restrict__ ci, const double* __restrict__ w,
+    const int* __restrict__ agg, const int* __restrict__ sizes, int k, int i,
+    int n, int si, int cap, unsigned int seed) {
+    PairCand c{0.0, 0u, -1};
+    int j = ci[k];
+    if (j == i || j >= n) return c;
+    double wk = w[k];
+    if (!(wk > 0.0) || agg[j] >= 0) return c;
+    if ((long long)si + sizes[j] > (long long)cap) return c;
+    c.w = wk;
+    c.h = pair_hash(i, j, seed);
+    c.j = j;
+    return c;
+}
+
+// prop[i] = other end of the largest eligible edge of an unaggregated row,
+// i itself if it has none, -1 for an aggregated row. One thread per row.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_propose_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const double* __restrict__ w, int n, const int* __restrict__ agg,
+    const int* __restrict__ sizes, int cap, unsigned int seed,
+    int* __restrict__ prop) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (agg[i] >= 0) { prop[i] = -1; return; }
+    int si = sizes[i];
+    PairCand best{0.0, 0u, -1};
+    for (int k = ro[i]; k < ro[i + 1]; ++k) {
+        PairCand c = match_cand(ci, w, agg, sizes, k, i, n, si, cap, seed);
+        if (cand_better(i, c, best)) best = c;
+    }
+    prop[i] = best.j >= 0 ? best.j : i;
+}
+
+// L lanes per row with a shuffle arg-max over the same total order, for the
+// wider rows of ghost-level graphs; gives exactly the thread-per-row
+// proposal. Built for L = 8: 32 lanes measured slower at every average degree
+// from 7 to 27 (profiles/NOTES.md).
+template <int L>
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_propose_vec_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const double* __restrict__ w, int n, const int* __restrict__ agg,
+    const int* __restrict__ sizes, int cap, unsigned int seed,
+    int* __restrict__ prop) {
+    const int lane = threadIdx.x & (L - 1);
+    long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t / L >= n) return;   // uniform over the L lanes of a row
+    int i = (int)(t / L);
+    if (agg[i] >= 0) {
+        if (lane == 0) prop[i] = -1;
+        return;
+    }
+    int si = sizes[i];
+    PairCand best{0.0, 0u, -1};
+    for (int k = ro[i] + lane; k < ro[i + 1]; k += L) {
+        PairCand c = match_cand(ci, w, agg, sizes, k, i, n, si, cap, seed);
+        if (cand_better(i, c, best)) best = c;
+    }
+#pragma unroll
+    for (int off = L / 2; off > 0; off >>= 1) {
+        PairCand o;
+        o.w = __shfl_down(best.w, off, L);
+        o.h = __shfl_down(best.h, off, L);
+        o.j = __shfl_down(best.j, off, L);
+        if (cand_better(i, o, best)) best = o;
+    }
+    if (lane == 0) prop[i] = best.j >= 0 ? best.j : i;
+}
+
+// Mutual proposals merge into the smaller row. Row i alone writes the state
+// of i and of its partner, so the kernel has no race and no atomic.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_match_kernel(
+    const int* __restrict__ prop, int n, int* __restrict__ agg,
+    int* __restrict__ sizes) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int j = prop[i];
+    if (j > i && prop[j] == i) {
+        agg[i] = i;
+        agg[j] = i;
+        sizes[i] += sizes[j];
+    }
+}
+
+// *count += rows with agg < 0: block reduction, one atomic per block
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_count_kernel(
+    const int* __restrict__ agg, int n, int* __restrict__ count) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c = block_reduce_sum<int>((i < n && agg[i] < 0) ? 1 : 0);
+    if (threadIdx.x == 0 && c > 0) atomicAdd(count, c);
+}
+
+// Entry k of leftover row i as a join candidate: an edge to an aggregated
+// row whose aggregate (root r) still fits i under the cap.
+__device__ __forceinline__ PairCand join_cand(
+    const int* __restrict__ ci, const double* __restrict__ w,
+    const int* __restrict__ agg, const int* __restrict__ sizes, int k, int i,
+    int n, int si, int cap, unsigned int seed) {
+    PairCand c{0.0, 0u, -1};
+    int j = ci[k];
+    if (j == i || j >= n) return c;
+    double wk = w[k];
+    if (!(wk > 0.0)) return c;
+    int r = agg[j];
+    if (r < 0) return c;
+    if (sizes && (long long)si + sizes[r] > (long long)cap) return c;
+    c.w = wk;
+    c.h = pair_hash(i, j, seed);
+    c.j = j;
+    return c;
+}
+
+// merge_singletons = 1, one double-buffered sweep: a leftover joins the
+// aggregate at the other end of its largest edge, as agg_in shows it.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_join_sweep_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const double* __restrict__ w, int n, const int* __restrict__ agg_in,
+    unsigned int seed, int* __restrict__ agg_out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int a = agg_in[i];
+    if (a < 0) {
+        PairCand best{0.0, 0u, -1};
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            PairCand c = join_cand(ci, w, agg_in, nullptr, k, i, n, 0, 0, seed);
+            if (cand_better(i, c, best)) best = c;
+        }
+        if (best.j >= 0) a = agg_in[best.j];
+    }
+    agg_out[i] = a;
+}
+
+// merge_singletons = 2, one capped round in three steps. Bid: a leftover
+// picks the root r of its largest fitting edge and raises bid_w[r] to the
+// weight's bit pattern, which orders like the weight for w > 0.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_bid_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const double* __restrict__ w, int n, const int* __restrict__ agg,
+    const int* __restrict__ sizes, int cap, unsigned int seed,
+    int* __restrict__ bid_root, unsigned long long* __restrict__ bid_w) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int r = -1;
+    if (agg[i] < 0) {
+        PairCand best{0.0, 0u, -1};
+        int si = sizes[i];
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            PairCand c = join_cand(ci, w, agg, sizes, k, i, n, si, cap, seed);
+            if (cand_better(i, c, best)) best = c;
+        }
+        if (best.j >= 0) {
+            r = agg[best.j];
+            unsigned long long bits =
+                (unsigned long long)__double_as_longlong(best.w);
+            bid_w[i] = bits;   // own slot: a leftover is never a root
+            atomicMax(&bid_w[r], bits);
+        }
+    }
+    bid_root[i] = r;
+}
+
+// Among the bidders that hold a root's largest weight the smallest row wins.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_bid_tie_kernel(
+    int n, const int* __restrict__ bid_root,
+    const unsigned long long* __restrict__ bid_w, int* __restrict__ bid_i) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int r = bid_root[i];
+    if (r >= 0 && bid_w[i] == bid_w[r]) atomicMin(&bid_i[r], i);
+}
+
+// A root accepts its winner and clears its slots for the next round; the
+// root's thread alone writes the root and the winner.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_accept_kernel(
+    int n, int* __restrict__ agg, int* __restrict__ sizes,
+    unsigned long long* __restrict__ bid_w, int* __restrict__ bid_i) {
+    int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    if (agg[r] != r) return;
+    int i = bid_i[r];
+    if (i < n) {
+        agg[i] = r;
+        sizes[r] += sizes[i];
+        bid_i[r] = n;
+    }
+    bid_w[r] = 0ull;
+}
+
+// Renumbering: flag the roots (agg[i] == i; a row still at -1 becomes its
+// own root), exclusive-scan the flags, map every row through its root's id
+// and add up the member sizes per aggregate with integer atomics.
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_root_flag_kernel(
+    int* __restrict__ agg, int n, int* __restrict__ ids) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    int f = 0;
+    if (i < n) {
+        if (agg[i] < 0) agg[i] = i;
+        f = agg[i] == i ? 1 : 0;
+    }
+    ids[i] = f;   // ids[n] = 0 closes the exclusive scan
+}
+
+__global__ __launch_bounds__(AMGX_BLOCK) void pairwise_renumber_kernel(
+    const int* __restrict__ agg, int n, const int* __restrict__ ids,
+    const int* __restrict__ sizes_in, int* __restrict__ agg_out,
+    int* __restrict__ sizes_out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int id = ids[agg[i]];
+    agg_out[i] = id;
+    atomicAdd(&sizes_out[id], sizes_in[i]);
+}
+
+template <typename T>
+void pairwise_weights(const int* ro, const int* ci, const T* va,
+                      const int* tidx, const T* diag, int n, int formula,
+                      double* w, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL((pairwise_weights_kernel<T>), dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, ro, ci, va, tidx, diag, n,
+                       formula, w);
+}
+
+void pairwise_propose(const int* ro, const int* ci, const double* w, int n,
+                      const int* agg, const int* sizes, int cap, int seed,
+                      int lanes, int* prop, hipStream_t s) {
+    if (n <= 0) return;
+    if (lanes == 8) {
+        hipLaunchKernelGGL((pairwise_propose_vec_kernel<8>),
+                           dim3(grid_1d((long long)n * 8)), dim3(AMGX_BLOCK),
+                           0, s, ro, ci, w, n, agg, sizes, cap,
+                           (unsigned)seed, prop);
+    } else if (lanes == 1) {
+        hipLaunchKernelGGL(pairwise_propose_kernel, dim3(grid_1d(n)),
+                           dim3(AMGX_BLOCK), 0, s, ro, ci, w, n, agg, sizes,
+                           cap, (unsigned)seed, prop);
+    } else {
+        throw std::runtime_error("pairwise_propose: lanes must be 1 or 8");
+    }
+}
+
+void pairwise_match(const int* prop, int n, int* agg, int* sizes,
+                    hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pairwise_match_kernel, dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, prop, n, agg, sizes);
+}
+
+void pairwise_count_unaggregated(const int* agg, int n, int* count,
+                                 hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pairwise_count_kernel, dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, agg, n, count);
+}
+
+void pairwise_join_sweep(const int* ro, const int* ci, const double* w, int n,
+                         const int* agg_in, int seed, int* agg_out,
+                         hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pairwise_join_sweep_kernel, dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, ro, ci, w, n, agg_in,
+                       (unsigned)seed, agg_out);
+}
+
+void pairwise_join_capped(const int* ro, const int* ci, const double* w, int n,
+                          int* agg, int* sizes, int cap, int seed,
+                          int* bid_root, unsigned long long* bid_w, int* bid_i,
+                          hipStream_t s) {
+    if (n <= 0) return;
+    dim3 g(grid_1d(n)), b(AMGX_BLOCK);
+    hipLaunchKernelGGL(pairwise_bid_kernel, g, b, 0, s, ro, ci, w, n, agg,
+                       sizes, cap, (unsigned)seed, bid_root, bid_w);
+    hipLaunchKernelGGL(pairwise_bid_tie_kernel, g, b, 0, s, n, bid_root, bid_w,
+                       bid_i);
+    hipLaunchKernelGGL(pairwise_accept_kernel, g, b, 0, s, n, agg, sizes,
+                       bid_w, bid_i);
+}
+
+size_t pairwise_renumber_tmp_bytes(int n) {
+    size_t bytes = 0;
+    int* p = nullptr;
+    (void)rocprim::exclusive_scan(nullptr, bytes, p, p, 0, (size_t)n + 1,
+                                  rocprim::plus<int>(), (hipStream_t)0);
+    return bytes;
+}
+
+void pairwise_renumber(int* agg, int n, const int* sizes_in, int* ids,
+                       void* tmp, size_t tmp_bytes, int* agg_out,
+                       int* sizes_out, hipStream_t s) {
+    hipLaunchKernelGGL(pairwise_root_flag_kernel,
+                       dim3(grid_1d((long long)n + 1)), dim3(AMGX_BLOCK), 0,
+                       s, agg, n, ids);
+    HIP_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, ids, ids, 0,
+                                      (size_t)n + 1, rocprim::plus<int>(),
+                                      s));
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pairwise_renumber_kernel, dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, agg, n, ids, sizes_in, agg_out,
+                       sizes_out);
 }
 
 // ============================================================ sort helpers
@@ -682,7 +1064,8 @@ void slab_split_fill(const int* ro_s, const int* ci_s, const int* rows,
 #define INSTANTIATE_SETUP(T)                                                   \
     AMGX_INSTANTIATE(agg_propose, T)                                           \
     AMGX_INSTANTIATE(agg_merge_singletons, T)                                  \
-    AMGX_INSTANTIATE(galerkin_agg, T)                                          \
+    AMGX_INSTANTIATE(pairwise_weights, T)                                      \
+    AMGX_INSTANTIATE(galerkin_agg, T)                                         \
     AMGX_INSTANTIATE(spgemm_esc, T)
 #define INSTANTIATE_SETUP_REAL(T) AMGX_INSTANTIATE(transpose_csr, T)
 

@@ -172,6 +172,29 @@ def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
     return _backend(A).size2_matching(A, max_iterations, deterministic, seed)
 
 
+def pairwise_weights(A, formula: int = 0):
+    """MULTI_PAIRWISE edge weights: one float64 per stored entry (i, j) of A,
+    0 where the entry is no edge (diagonal, halo column, no stored (j, i),
+    zero divisor). formula 0: 0.5(|a_ij|+|a_ji|)/max(|a_ii|,|a_jj|);
+    formula 1: -0.5(a_ij/a_ii + a_ji/a_jj), scalar real matrices only.
+    Reference: src/aggregation/selectors/multi_pairwise.cu computeEdgeWeights.
+    The host version is the per-row oracle of the device kernel."""
+    return _backend(A).pairwise_weights(A, formula)
+
+
+def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
+                      merge_singletons, max_iterations, max_unassigned, seed):
+    """One MULTI_PAIRWISE pass on the weight graph (structure + w): capped
+    handshake rounds, the leftover phase of ``merge_singletons`` (0/1/2) and
+    the renumbering -> (aggregates int32 (n,), num, sizes int32 (num,),
+    rounds). ``sizes``: int32 (n,) node sizes; ``cap`` <= 0 or None: no cap.
+    The rules are stated in docs/KERNELS.md; host and device follow them to
+    the same result."""
+    return _backend(w).pairwise_matching(
+        row_offsets, col_indices, w, n, sizes, cap, merge_singletons,
+        max_iterations, max_unassigned, seed)
+
+
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
                          ncols_mod=None, generator=None):
     """Coarse A for piecewise-constant aggregation P:

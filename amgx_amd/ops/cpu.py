@@ -360,6 +360,169 @@ def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
     return torch.from_numpy(agg.astype(np.int32)), int(next_id)
 
 
+# MULTI_PAIRWISE oracle: per-row loops in float64 that follow the rules of
+# docs/KERNELS.md ("MULTI_PAIRWISE") literally. The device kernels are
+# tested for exact equality against these; they are written for reading.
+_U32 = 0xFFFFFFFF
+
+
+def _hash_u32(a: int, seed: int) -> int:
+    """hash_u32 of kernels_setup.hip on Python integers."""
+    a = (a ^ seed) & _U32
+    a = ((a ^ 61) ^ (a >> 16)) & _U32
+    a = (a * 9) & _U32
+    a ^= a >> 4
+    a = (a * 0x27D4EB2D) & _U32
+    a ^= a >> 15
+    return a
+
+
+def _pair_hash(i: int, j: int, seed: int) -> int:
+    lo, hi = min(i, j), max(i, j)
+    return _hash_u32(_hash_u32(lo, seed) ^ hi, seed)
+
+
+def _absd(v) -> float:
+    """|v| in double; the modulus of a complex value from its two parts."""
+    if isinstance(v, complex):
+        return float(np.sqrt(np.float64(v.real) * np.float64(v.real)
+                             + np.float64(v.imag) * np.float64(v.imag)))
+    return abs(v)
+
+
+def pairwise_weights(A, formula: int = 0) -> torch.Tensor:
+    """One double per stored entry (i, j): the MULTI_PAIRWISE edge weight,
+    0 for the diagonal, a halo column, a missing (j, i) or a zero divisor."""
+    if formula not in (0, 1):
+        raise ValueError("weight_formula must be 0 or 1")
+    if A.values.is_complex() and A.block_dim > 1:
+        raise NotImplementedError(
+            "aggregation of a block matrix is not available in the complex "
+            "modes")
+    if formula == 1 and (A.values.is_complex() or A.block_dim > 1):
+        raise NotImplementedError(
+            "weight_formula 1 is signed: scalar real matrices only")
+    n = A.n_rows
+    ro = _np(A.row_offsets).astype(np.int64)
+    ci = _np(A.col_indices).astype(np.int64)
+    vals = _np(A.values)
+    if A.block_dim > 1:   # Frobenius norm of each block, as size2_matching
+        vals = np.sqrt((vals.astype(np.float64) ** 2).sum(axis=(1, 2)))
+    # widen first: fp32 -> double, complex64 -> complex128
+    va = [complex(v) if np.iscomplexobj(vals) else float(v) for v in vals]
+    pos = [{int(ci[k]): k for k in range(ro[i], ro[i + 1])} for i in range(n)]
+    diag = [va[pos[i][i]] if i in pos[i] else 0.0 for i in range(n)]
+    w = np.zeros(ci.size, dtype=np.float64)
+    for i in range(n):
+        for k in range(ro[i], ro[i + 1]):
+            j = int(ci[k])
+            if j == i or j >= n or i not in pos[j]:
+                continue
+            t = pos[j][i]
+            if formula == 0:
+                m = max(_absd(diag[i]), _absd(diag[j]))
+                if m > 0.0:
+                    w[k] = 0.5 * (_absd(va[k]) + _absd(va[t])) / m
+            elif diag[i] != 0.0 and diag[j] != 0.0:
+                w[k] = -0.5 * (va[k] / diag[i] + va[t] / diag[j])
+    return torch.from_numpy(w)
+
+
+def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
+                      merge_singletons, max_iterations, max_unassigned, seed):
+    """One MULTI_PAIRWISE pass on the weight graph: handshake rounds, the
+    leftover phase of ``merge_singletons`` and the renumbering. Returns
+    (agg int32[n], num, sizes int32[num], rounds)."""
+    if merge_singletons not in (0, 1, 2):
+        raise ValueError("merge_singletons must be 0, 1 or 2")
+    ro = [int(v) for v in _np(row_offsets)]
+    ci = [int(v) for v in _np(col_indices)]
+    w = [float(v) for v in _np(w)]
+    cur = [int(v) for v in _np(sizes)]
+    seed = int(seed) & 0x7FFFFFFF
+    cap =int(cap) if cap and cap > 0 else None
+    agg = [-1] * n
+
+    def edges(i):
+        for k in range(ro[i], ro[i + 1]):
+            if ci[k] != i and ci[k] < n and w[k] > 0.0:
+                yield k, ci[k]
+
+    def key(i, k):
+        j = ci[k]
+        return (w[k], _pair_hash(i, j, seed), min(i, j), max(i, j))
+
+    def largest(i, ok):
+        best = None
+        for k, j in edges(i):
+            if ok(j) and (best is None or key(i, k) > key(i, best)):
+                best = k
+        return best
+
+    def fits(i, r):
+        return cap is None or cur[i] + cur[r] <= cap
+
+    # ---- matching rounds
+    un, rounds = n, 0
+    while (rounds < max_iterations and un > 0
+           and not un < max_unassigned * n):
+        prop = [-1] * n
+        for i in range(n):
+            if agg[i] < 0:
+                k = largest(i, lambda j: agg[j] < 0 and fits(i, j))
+                prop[i] = ci[k] if k is not None else i
+        pairs = 0
+        for i in range(n):
+            j = prop[i]
+            if j > i and prop[j] == i:
+                agg[i] = agg[j] = i
+                cur[i] += cur[j]
+                pairs += 1
+        rounds += 1
+        if pairs == 0:
+            break
+        un -= 2 * pairs
+
+    # ---- leftovers
+    if merge_singletons == 1:
+        while True:
+            new = list(agg)
+            for i in range(n):
+                if agg[i] < 0:
+                    k = largest(i, lambda j: agg[j] >= 0)
+                    if k is not None:
+                        new[i] = agg[ci[k]]
+                        cur[new[i]] += cur[i]
+            if new == agg:
+                break
+            agg = new
+    elif merge_singletons == 2:
+        while True:
+            bids = {}
+            for i in range(n):
+                if agg[i] < 0:
+                    k = largest(i, lambda j: agg[j] >= 0 and fits(i, agg[j]))
+                    if k is not None:
+                        bids.setdefault(agg[ci[k]], []).append((w[k], i))
+            if not bids:
+                break
+            for r, lst in bids.items():
+                wmax = max(wk for wk, _ in lst)
+                i = min(i for wk, i in lst if wk == wmax)
+                agg[i] = r
+                cur[r] += cur[i]
+    for i in range(n):
+        if agg[i] < 0:
+            agg[i] = i
+
+    # ---- renumber: roots in ascending order
+    roots = [i for i in range(n) if agg[i] == i]
+    ids = {r: t for t, r in enumerate(roots)}
+    out = np.array([ids[a] for a in agg], dtype=np.int32).reshape(n)
+    szs = np.array([cur[r] for r in roots], dtype=np.int32).reshape(len(roots))
+    return (torch.from_numpy(out), len(roots), torch.from_numpy(szs), rounds)
+
+
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
                          ncols_mod=None, generator=None):
     # generator: the host path has a single sort/reduce implementation

@@ -419,6 +419,40 @@ def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
     return agg.to(torch.int32), int(uniq.numel())
 
 
+def pairwise_weights(A, formula: int = 0):
+    if A.block_dim > 1 and A.values.is_complex():
+        raise NotImplementedError(
+            "aggregation of a block matrix is not available in the complex "
+            "modes (dZZI / dCCI / dZCI)")
+    if formula == 1 and (A.values.is_complex() or A.block_dim > 1):
+        raise NotImplementedError(
+            "weight_formula 1 is signed: scalar real matrices only")
+    if A.block_dim > 1:
+        # Frobenius norm of each block, in double; the diagonal "value" is
+        # the norm of the diagonal block
+        va = torch.linalg.vector_norm(
+            A.values.reshape(A.nnz, -1).to(torch.float64), dim=1)
+        didx = _didx(A).long()
+        diag = torch.where(didx >= 0, va[didx.clamp(min=0)],
+                           torch.zeros((), dtype=va.dtype, device=va.device))
+    else:
+        va, diag = A.values, extract_diagonal(A)
+    return _core.pairwise_weights(A.row_offsets, A.col_indices, va, _tidx(A),
+                                  diag.contiguous(), A.n_rows, int(formula))
+
+
+def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
+                      merge_singletons, max_iterations, max_unassigned, seed,
+                      lanes: int = 0):
+    """lanes: lanes per row of the propose kernel (1 or 8; 0 = routed by
+    average degree). Both give the same result."""
+    agg, num, szs, rounds = _core.pairwise_match(
+        row_offsets, col_indices, w, int(n), sizes, int(cap or 0),
+        int(merge_singletons), int(max_iterations), float(max_unassigned),
+        int(seed) & 0x7FFFFFFF, int(lanes))
+    return agg, int(num), szs, int(rounds)
+
+
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
                          ncols_mod=None, generator=None):
     """agg_col/ncols_mod: distributed variant — per-column coarse ids (GLOBAL)

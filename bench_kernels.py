@@ -7,7 +7,7 @@ SpGEMM, transpose) on a 3D Poisson problem, reporting ms and achieved GB/s
 against the analytic bytes-moved model. One JSON line per kernel to stdout;
 human table to stderr.
 
-    python bench_kernels.py [--size 192] [--iters 20]
+    python bench_kernels.py [--size 192] [--iters 20] [--section multi_pairwise]
 """
 
 import argparse
@@ -28,10 +28,70 @@ def bench(fn, iters, sync):
     return (time.perf_counter() - t0) / iters
 
 
+def bench_multi_pairwise(A, iters, sync, rec):
+    """MULTI_PAIRWISE on the device: the selector at 1, 2 and 3 passes next
+    to SIZE_2 / SIZE_4 / SIZE_8 (equal pass counts), and the propose kernel
+    in its thread-per-row and 8-lane forms on the graph of each
+    pass (g1 = the matrix graph, g3 = the pass-3 ghost graph), on the
+    benchmark's 7-point matrix and on a 27-point one."""
+    from amgx_amd.amg.aggregation import AGG_SELECTOR_REGISTRY
+    from amgx_amd.config import ConfigScope
+
+    it = max(iters // 8, 1)
+    for p, sized in ((1, "SIZE_2"), (2, "SIZE_4"), (3, "SIZE_8")):
+        sc = ConfigScope(None, {"aggregation_passes": p,
+                                "merge_singletons": 2})
+        rec(f"multi_pairwise_select_p{p}", bench(
+            lambda: AGG_SELECTOR_REGISTRY["MULTI_PAIRWISE"](A, sc), it, sync))
+        rec(f"{sized.lower()}_select", bench(
+            lambda: AGG_SELECTOR_REGISTRY[sized](A, ConfigScope(None, {})),
+            it, sync))
+    propose_records(A, "", iters, sync, rec)
+    # the wider graphs of a 27-point stencil
+    from amgx_amd.problems import poisson_3d_27pt
+    side = min(round(A.n_rows ** (1.0 / 3.0)), 128)
+    propose_records(poisson_3d_27pt(side, side, side, device=A.device),
+                    "27pt_", iters, sync, rec)
+
+
+def propose_records(A, tag, iters, sync, rec):
+    """pairwise_propose with 1 and 8 lanes per row on the graph of each
+    of three MULTI_PAIRWISE passes on A, every row unaggregated (the first
+    and heaviest round)."""
+    from amgx_amd import _core, ops
+    from amgx_amd.amg.aggregation import multi_pairwise_passes
+    from amgx_amd.config import ConfigScope
+    from amgx_amd.matrix import CSRMatrix
+
+    sc = ConfigScope(None, {"aggregation_passes": 3, "merge_singletons": 2})
+    _, _, levels = multi_pairwise_passes(A, sc, return_levels=True)
+    ro, ci, n = A.row_offsets, A.col_indices, A.n_rows
+    w = ops.pairwise_weights(A, 0)
+    sizes = torch.ones(n, dtype=torch.int32, device=w.device)
+    for p, (level_agg, num, level_sizes, _) in enumerate(levels, 1):
+        agg = torch.full((n,), -1, dtype=torch.int32, device=w.device)
+        nnz = ci.numel()
+        print(f"{tag}pass-{p} graph: {n} rows, {nnz / max(n, 1):.1f} "
+              f"entries/row", file=sys.stderr)
+        for lanes in (1, 8):
+            rec(f"pairwise_propose_{tag}g{p}_l{lanes}", bench(
+                lambda: _core.pairwise_propose(ro, ci, w, n, agg, sizes, 10,
+                                               p - 1, lanes), iters, sync),
+                nnz * 12 + (n + 1) * 4 + n * 12)
+        if p < len(levels):
+            G = ops.galerkin_aggregation(CSRMatrix(ro, ci, w, n_cols=n),
+                                         level_agg, num)
+            ro, ci, w, n = G.row_offsets, G.col_indices, G.values, num
+            sizes = level_sizes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=192)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--section", default="all",
+                    choices=("all", "multi_pairwise"),
+                    help="multi_pairwise: only the MULTI_PAIRWISE records")
     args = ap.parse_args()
     sys.path.insert(0, ".")
     from amgx_amd import ops
@@ -58,6 +118,12 @@ def main():
         gbps = bytes_moved / sec / 1e9 if bytes_moved else None
         results[name] = {"ms": sec * 1e3, "GBps": gbps}
         print(json.dumps({"kernel": name, "ms": sec * 1e3, "GBps": gbps}))
+
+    if args.section == "multi_pairwise":
+        if dev == "cpu":
+            sys.exit("--section multi_pairwise times device kernels: no GPU")
+        bench_multi_pairwise(A, args.iters, sync, rec)
+        return
 
     rec("csrmv", bench(lambda: ops.spmv(A, x, y), args.iters, sync),
         spmv_bytes)
@@ -154,6 +220,8 @@ def main():
         max(args.iters // 8, 1), sync))
     rec("transpose", bench(lambda: ops.transpose(A),
                            max(args.iters // 8, 1), sync))
+    if dev != "cpu":   # the host selector is an interpreted loop
+        bench_multi_pairwise(A, args.iters, sync, rec)
     print("kernel              ms         GB/s", file=sys.stderr)
     for k, v in results.items():
         gb = f"{v['GBps']:.0f}" if v["GBps"] else "-"
