@@ -544,17 +544,38 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
     });
 }
 
+// lanes per row of the scalar per-color DILU sweeps, from a slab's average
+// entries per row: thread-per-row up to the threshold, 8 lanes above.
+// Measured on MI355X (profiles/NOTES.md, "DILU one gathered vector and lane
+// forms"): over the split parts L and U one lane wins at 2.98 entries per
+// row and 8 lanes from 4.57 upwards. Over the full slab 8 lanes win at every
+// figure measured (6.97, 10.14, 12.63); its threshold stays at the 8 of the
+// propose kernel, which keeps 7-point matrices on one lane.
+constexpr double DILU_LANES_THRESHOLD_FULL = 8.0;
+constexpr double DILU_LANES_THRESHOLD_SPLIT = 4.0;
+int64_t dilu_lanes(double entries_per_row, bool split) {
+    double t = split ? DILU_LANES_THRESHOLD_SPLIT : DILU_LANES_THRESHOLD_FULL;
+    return entries_per_row <= t ? 1 : 8;
+}
+
 // per-color scalar DILU apply x += relax * M^{-1} rhs over the strict
-// color-split slabs; w is the one scratch vector (column-extended).
+// color-split slabs; w is the scratch vector (column-extended).
 // fused: rhs is b, the forward sweep reads the full slab (ro_f, ci_f, va_f)
-// with the residual b - A x folded in and needs w zeroed. Plain: the forward
-// sweep reads the L slab (same three arguments) and w needs no zeroing.
-// The backward sweep runs in place in w over the U slab and updates x as it
-// goes. No allocation and no host sync: capturable in a hipGraph.
+// with the residual b - A x folded in through the second scratch vector
+// y = x + w (column-extended like w; taken from the caller so that nothing
+// is allocated under graph capture, allocated here when absent). Plain: the
+// forward sweep reads the L slab (same three arguments). Neither scratch
+// vector needs zeroing. The backward sweep runs in place in w over the U slab
+// and updates x as it goes. No host sync: capturable in a hipGraph.
+// lanes: 0 routes each slab by its entries per row (dilu_lanes; the entry
+// counts are the tensors' sizes, no read-back; the forward slab of a plain
+// apply and U are split parts), 1 or 8 forces that form for both sweeps
+// (tests and bench_kernels.py).
 void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                 Tensor ci_u, Tensor va_u, Tensor einv_s, Tensor rows_sorted,
                 std::vector<int64_t> bounds, Tensor rhs, Tensor w, Tensor x,
-                double relax, bool fused) {
+                double relax, bool fused, int64_t lanes,
+                c10::optional<Tensor> y_opt) {
     int64_t n = (int64_t)ro_u.numel() - 1;
     TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
                     einv_s.numel() == n,
@@ -571,28 +592,47 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                     va_u.scalar_type() == va_f.scalar_type() &&
                     einv_s.scalar_type() == va_f.scalar_type(),
                 "dilu_split: mixed value types");
-    if (fused) w.zero_();
+    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
+                "dilu_split: lanes must be 0 (routed), 1 or 8");
+    Tensor y;
+    if (fused) {
+        y = y_opt.has_value() ? *y_opt : torch::empty_like(w);
+        TORCH_CHECK(y.is_contiguous() && y.device() == x.device() &&
+                        y.scalar_type() == x.scalar_type() &&
+                        y.numel() >= x.numel(),
+                    "dilu_split: y must be a vector like w");
+    }
+    double rows = (double)std::max<int64_t>(n, 1);
+    int lanes_f = lanes ? (int)lanes
+                        : (int)dilu_lanes((double)ci_f.numel() / rows, !fused);
+    int lanes_u = lanes ? (int)lanes
+                        : (int)dilu_lanes((double)ci_u.numel() / rows, true);
     DISPATCH(AMGX_VALUE_PAIRS, "dilu_split", (va_f, x), [&] {
         hipStream_t st = cur_stream();
+        if (fused)
+            amgx_hip::dilu_y_init<scalar_v>(dptr<scalar_v>(x),
+                                            dptr<scalar_v>(y),
+                                            (long long)x.numel(), st);
         for_each_color(bounds, true, [&](int, int64_t s, int64_t e) {
             if (fused)
-                amgx_hip::dilu_fwd_sorted<scalar_a, scalar_v>(
+                amgx_hip::dilu_fwd_full<scalar_a, scalar_v>(
                     iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                     (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(x),
-                    dptr<scalar_v>(w), 1, st);
+                    dptr<scalar_v>(w), dptr<scalar_v>(y), lanes_f, st);
             else
                 amgx_hip::dilu_fwd_lower<scalar_a, scalar_v>(
                     iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
-                    (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(w), st);
+                    (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(w),
+                    lanes_f, st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_bwd_upper<scalar_a, scalar_v>(
                 iptr(ro_u) + s, iptr(ci_u), dptr<scalar_a>(va_u),
                 dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                 (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(x),
-                (scalar_v)relax, st);
+                (scalar_v)relax, lanes_u, st);
         });
     });
 }
@@ -1115,7 +1155,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gs_sweep_sorted", &gs_sweep_sorted);
     m.def("dilu_setup", &dilu_setup);
     m.def("dilu_sorted", &dilu_sorted);
-    m.def("dilu_split", &dilu_split);
+    {   // trailing lanes / y are optional: 14 positional arguments still work
+        using pybind11::arg;
+        m.def("dilu_split", &dilu_split, arg("ro_f"), arg("ci_f"),
+              arg("va_f"), arg("ro_u"), arg("ci_u"), arg("va_u"),
+              arg("einv_s"), arg("rows_sorted"), arg("bounds"), arg("rhs"),
+              arg("w"), arg("x"), arg("relax"), arg("fused"),
+              arg("lanes") = 0, arg("y") = pybind11::none());
+    }
+    m.def("dilu_lanes", &dilu_lanes, pybind11::arg("entries_per_row"),
+          pybind11::arg("split") = false);
     m.def("slab_split", &slab_split);
     m.def("color_minmax", &color_minmax);
     m.def("size2_match", &size2_match);

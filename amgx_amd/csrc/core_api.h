@@ -128,8 +128,8 @@ void gs_rows_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                     int count, TV omega, hipStream_t s);
 
 // DILU: x += relax * M^{-1} rhs.  Fused-residual form: rhs = b and the
-// forward gather adds x (xres), so M^{-1}(b - A x) costs one matrix read
-// less; scalar and block-4 only.
+// forward sweep folds the residual in, so M^{-1}(b - A x) costs one matrix
+// read less; scalar and block-4 only.
 // whole apply for small scalar levels: zeroing, all forward colors, all
 // backward colors and the relaxed axpy
 template <typename TA, typename TV>
@@ -137,6 +137,8 @@ void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
                 const TA* einv_s, const int* rows, const int* bounds,
                 int ncolors, const TV* rhs, TV* w, TV* z, TV* x, TV relax,
                 long long vec_n, bool fused, hipStream_t s);
+// block matrices only; xres (block-4) folds the residual in by gathering
+// xres + w over a pre-zeroed w
 template <typename TA, typename TV>
 void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
@@ -146,19 +148,30 @@ template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s);
-// Scalar per-color sweeps over the strict color-split slabs (slab_split_*):
-// plain forward w_i = Einv_i (rhs_i - sum_L a_ij w_j), no pre-zeroed w;
-// backward in place z_i = w_i - Einv_i sum_U a_ij w_j stored to w[i], with
-// x[i] += relax * z_i folded in. ro_l / ro_u / rows / einv_s pre-offset to
-// the color base.
+// Scalar per-color sweeps, with lanes = 1 or 8 lanes per row (same bits);
+// ro_* / rows / einv_s pre-offset to the color base.
+// Fused forward over the full slab: dilu_y_init writes y = x + 0 over the
+// column-extended length once per apply, then per color
+// w_i = Einv_i (rhs_i - sum a_ij y_j), y_i = x_i + w_i; neither w nor y needs
+// zeroing. Over the strict color-split slabs (slab_split_*): plain forward
+// w_i = Einv_i (rhs_i - sum_L a_ij w_j), no pre-zeroed w; backward in place
+// z_i = w_i - Einv_i sum_U a_ij w_j stored to w[i], with x[i] += relax * z_i
+// folded in.
+template <typename TV>
+void dilu_y_init(const TV* x, TV* y, long long n, hipStream_t s);
+template <typename TA, typename TV>
+void dilu_fwd_full(const int* ro_s, const int* ci_s, const TA* va_s,
+                   const TA* einv_s, const int* rows, int count,
+                   const TV* rhs, const TV* x, TV* w, TV* y, int lanes,
+                   hipStream_t s);
 template <typename TA, typename TV>
 void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
                     const TA* einv_s, const int* rows, int count,
-                    const TV* rhs, TV* w, hipStream_t s);
+                    const TV* rhs, TV* w, int lanes, hipStream_t s);
 template <typename TA, typename TV>
 void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
                     const TA* einv_s, const int* rows, int count, TV* w,
-                    TV* x, TV relax, hipStream_t s);
+                    TV* x, TV relax, int lanes, hipStream_t s);
 // Einv of the rows of one color (colors ascending)
 template <typename T>
 void dilu_setup_color(const int* ro, const int* ci, const T* va,

@@ -129,6 +129,12 @@ template <typename R> struct real_of<cplx<R>> { using type = R; };
 // inside this namespace
 using ::__shfl_down;
 using ::__shfl_xor;
+using ::__shfl;
+template <typename R>
+__device__ __forceinline__ cplx<R> __shfl(const cplx<R>& v, int src,
+                                          int width = warpSize) {
+    return cplx<R>(::__shfl(v.re, src, width), ::__shfl(v.im, src, width));
+}
 template <typename R>
 __device__ __forceinline__ cplx<R> __shfl_down(const cplx<R>& v, unsigned off,
                                                int width = warpSize) {

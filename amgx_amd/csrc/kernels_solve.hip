@@ -506,20 +506,15 @@ void jacobi_smooth(const int* ro, const int* ci, const TA* va, const TA* dinv,
 }
 
 // ============================================================ multicolor sweeps
-// Row product of slot t of a color-sorted slab with the gathered vector v
-// (FUSED: with xres + v, which folds a residual into the product). The
-// first 8 entries are peeled so their loads issue together; summation
+// Row product of slot t of a color-sorted slab with the gathered vector v.
+// The first 8 entries are peeled so their loads issue together; summation
 // runs in ascending k.
-template <bool FUSED, typename TA, typename TV>
+template <typename TA, typename TV>
 __device__ __forceinline__ TV slab_row_dot(const int* __restrict__ ro_s,
                                            const int* __restrict__ ci_s,
                                            const TA* __restrict__ va_s, int t,
-                                           const TV* v,
-                                           const TV* xres = nullptr) {
-    auto term = [&](int k) {
-        int j = ci_s[k];
-        return (TV)va_s[k] * (FUSED ? xres[j] + v[j] : v[j]);
-    };
+                                           const TV* v) {
+    auto term = [&](int k) { return (TV)va_s[k] * v[ci_s[k]]; };
     int k = ro_s[t], e = ro_s[t + 1];
     TV sum = TV(0);
 #pragma unroll
@@ -528,6 +523,43 @@ __device__ __forceinline__ TV slab_row_dot(const int* __restrict__ ro_s,
     }
     for (; k < e; ++k) sum += term(k);
     return sum;
+}
+
+// The same product with LANES lanes per row (a power of two, the lanes of
+// one row adjacent in the wave): per chunk of LANES entries lane l loads
+// entry k0 + l, so the slab reads coalesce and the gathers of a chunk are in
+// flight together; the chunk is then folded in ascending k from values
+// broadcast within the group, every lane carrying the same sum. Entries past
+// the row's end are skipped, not added as zeros, and the product-and-add is
+// the expression of slab_row_dot, so the sum is that of the one-lane form
+// bit for bit. All LANES lanes of a row must call this together.
+template <int LANES, typename TA, typename TV>
+__device__ __forceinline__ TV slab_row_dot_lanes(const int* __restrict__ ro_s,
+                                                 const int* __restrict__ ci_s,
+                                                 const TA* __restrict__ va_s,
+                                                 int t, int lane,
+                                                 const TV* v) {
+    if constexpr (LANES == 1) {
+        return slab_row_dot(ro_s, ci_s, va_s, t, v);
+    } else {
+        const int e = ro_s[t + 1];
+        TV sum = TV(0);
+        for (int k0 = ro_s[t]; k0 < e; k0 += LANES) {
+            TA a = TA(0);
+            TV g = TV(0);
+            if (k0 + lane < e) {
+                a = va_s[k0 + lane];
+                g = v[ci_s[k0 + lane]];
+            }
+#pragma unroll
+            for (int u = 0; u < LANES; ++u) {
+                TA au = __shfl(a, u, LANES);
+                TV gu = __shfl(g, u, LANES);
+                if (k0 + u < e) sum += (TV)au * gu;
+            }
+        }
+        return sum;
+    }
 }
 
 // ============================================================ multicolor GS
@@ -543,7 +575,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void gs_rows_scalar_sorted(
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     int i = rows[t];
-    TV sum = slab_row_dot<false>(ro_s, ci_s, va_s, t, x);
+    TV sum = slab_row_dot(ro_s, ci_s, va_s, t, x);
     x[i] += omega * (TV)dinv_s[t] * (bvec[i] - sum);
 }
 
@@ -790,37 +822,72 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
 // local columns, U those of later colors, both in slab order, so the sums
 // below run in the order of a full-row product with the zero terms left out.
 //
-// fused forward (full slab): w_i = Einv_i (b_i - sum_k a_k (x_k + w_k)), w
-// pre-zeroed so the product only picks up earlier colors (valid coloring =>
-// no same-color off-diagonals; diagonal contributes w_i = 0).  The single
-// gather x[j]+w[j] replaces residual kernel + sweep with one matrix read,
-// mathematically identical to r = b - A x; M w = r.
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_sorted(
+// The three scalar kernels take LANES lanes per row (slab_row_dot_lanes): one
+// where rows are short, 8 where they are long (the Galerkin levels); lane 0
+// does the row's own reads and writes, and both forms give the same bits.
+//
+// fused forward (full slab): w_i = Einv_i (b_i - sum_k a_k y_k) with the one
+// gathered vector y = x + w kept next to w: dilu_y_init writes y = x + 0 (the
+// value x_k + w_k had under a zeroed w, sign of zero included) and each row
+// stores y_i = x_i + w_i with its w_i, the sum rounded on its own as the
+// gathered x[j] + w[j] was. The product so only picks up earlier colors
+// (valid coloring => no same-color off-diagonals; the diagonal meets y_i =
+// x_i). It replaces residual kernel + sweep with one matrix read,
+// mathematically identical to r = b - A x; M w = r; nothing reads a w or y
+// that this apply has not written.
+template <typename T>
+__device__ __forceinline__ T add_unfused(T a, T b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+template <typename R>
+__device__ __forceinline__ cplx<R> add_unfused(const cplx<R>& a,
+                                               const cplx<R>& b) {
+#pragma clang fp contract(off)
+    return cplx<R>(a.re + b.re, a.im + b.im);
+}
+
+template <typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_y_init_kernel(
+    const TV* __restrict__ x, TV* __restrict__ y, long long n) {
+    long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) y[j] = x[j] + TV(0);
+}
+
+template <int LANES, typename TA, typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_full(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
     const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
     const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
-    const TV* __restrict__ xres, TV* __restrict__ w) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
+    const TV* __restrict__ x, TV* __restrict__ w, TV* y) {
+    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g / LANES >= count) return;   // uniform over the lanes of a row
+    int t = (int)(g / LANES);
+    int lane = threadIdx.x & (LANES - 1);
+    TV sum = slab_row_dot_lanes<LANES>(ro_s, ci_s, va_s, t, lane, y);
+    if (lane != 0) return;
     int i = rows[t];
-    TV sum = slab_row_dot<true>(ro_s, ci_s, va_s, t, w, xres);
-    w[i] = (TV)einv_s[t] * (rhs[i] - sum);
+    TV wi = (TV)einv_s[t] * (rhs[i] - sum);
+    w[i] = wi;
+    y[i] = add_unfused(x[i], wi);
 }
 
 // plain forward over L: w_i = Einv_i (rhs_i - sum_L A_ij w_j).  Only rows of
 // earlier colors, already written by this sweep, are read: w needs no
 // zeroing.
-template <typename TA, typename TV>
+template <int LANES, typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_lower(
     const int* __restrict__ ro_l, const int* __restrict__ ci_l,
     const TA* __restrict__ va_l, const TA* __restrict__ einv_s,
     const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
     TV* w) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
+    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g / LANES >= count) return;
+    int t = (int)(g / LANES);
+    int lane = threadIdx.x & (LANES - 1);
+    TV sum = slab_row_dot_lanes<LANES>(ro_l, ci_l, va_l, t, lane, w);
+    if (lane != 0) return;
     int i = rows[t];
-    TV sum = slab_row_dot<false>(ro_l, ci_l, va_l, t, w);
     w[i] = (TV)einv_s[t] * (rhs[i] - sum);
 }
 
@@ -829,16 +896,19 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_lower(
 // z_i overwrites w_i; the relaxed update x_i += relax z_i (the axpy
 // expression) rides along since the sweep never reads x.  The last color's
 // U rows are empty: its launch reads ro_u, w and x only.
-template <typename TA, typename TV>
+template <int LANES, typename TA, typename TV>
 __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_upper(
     const int* __restrict__ ro_u, const int* __restrict__ ci_u,
     const TA* __restrict__ va_u, const TA* __restrict__ einv_s,
     const int* __restrict__ rows, int count, TV* w, TV* __restrict__ x,
     TV relax) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
+    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g / LANES >= count) return;
+    int t = (int)(g / LANES);
+    int lane = threadIdx.x & (LANES - 1);
+    TV sum = slab_row_dot_lanes<LANES>(ro_u, ci_u, va_u, t, lane, w);
+    if (lane != 0) return;
     int i = rows[t];
-    TV sum = slab_row_dot<false>(ro_u, ci_u, va_u, t, w);
     TV z = w[i] - (TV)einv_s[t] * sum;
     w[i] = z;
     x[i] += relax * z;
@@ -962,9 +1032,9 @@ void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
                        vec_n);
 }
 
-// xres != nullptr selects the fused-residual sweep (rhs = b, xres = x);
-// there is no fused kernel for generic block sizes, and the plain scalar
-// sweep runs over the L slab (dilu_fwd_lower) instead (caller guards both)
+// block matrices only (xres != nullptr selects the fused-residual sweep of
+// block-4, rhs = b and xres = x; there is no fused kernel for generic block
+// sizes); the scalar forward sweeps are dilu_fwd_full and dilu_fwd_lower
 template <typename TA, typename TV>
 void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
@@ -972,13 +1042,9 @@ void dilu_fwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      hipStream_t s) {
     if (count <= 0) return;
     if (b == 1) {
-        if (!xres)
-            throw std::runtime_error(
-                "dilu_fwd_sorted: the plain scalar sweep is dilu_fwd_lower");
-        hipLaunchKernelGGL((dilu_fwd_scalar_sorted<TA, TV>),
-                           dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s,
-                           ro_s, ci_s, va_s, einv_s, rows, count, rhs, xres,
-                           w);
+        throw std::runtime_error(
+            "dilu_fwd_sorted: the scalar sweeps are dilu_fwd_full and "
+            "dilu_fwd_lower");
     } else if constexpr (is_cplx<TV>::value) {
         throw std::runtime_error(
             "dilu_fwd_sorted: complex block matrices are unsupported");
@@ -1014,25 +1080,55 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
     }
 }
 
+// LANES of a scalar per-color launch: 1 or 8 lanes per row
+#define DILU_LANES_LAUNCH(kernel, lanes, count, s, ...)                        \
+    do {                                                                       \
+        if ((lanes) == 8)                                                      \
+            hipLaunchKernelGGL((kernel<8, TA, TV>),                            \
+                               dim3(grid_1d((long long)(count) * 8)),          \
+                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
+        else if ((lanes) == 1)                                                 \
+            hipLaunchKernelGGL((kernel<1, TA, TV>), dim3(grid_1d(count)),      \
+                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
+        else                                                                   \
+            throw std::runtime_error(#kernel ": lanes must be 1 or 8");        \
+    } while (0)
+
+template <typename TV>
+void dilu_y_init(const TV* x, TV* y, long long n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL((dilu_y_init_kernel<TV>), dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, x, y, n);
+}
+
+template <typename TA, typename TV>
+void dilu_fwd_full(const int* ro_s, const int* ci_s, const TA* va_s,
+                   const TA* einv_s, const int* rows, int count,
+                   const TV* rhs, const TV* x, TV* w, TV* y, int lanes,
+                   hipStream_t s) {
+    if (count <= 0) return;
+    DILU_LANES_LAUNCH(dilu_fwd_scalar_full, lanes, count, s, ro_s, ci_s, va_s,
+                      einv_s, rows, count, rhs, x, w, y);
+}
+
 template <typename TA, typename TV>
 void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
                     const TA* einv_s, const int* rows, int count,
-                    const TV* rhs, TV* w, hipStream_t s) {
+                    const TV* rhs, TV* w, int lanes, hipStream_t s) {
     if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_fwd_scalar_lower<TA, TV>), dim3(grid_1d(count)),
-                       dim3(AMGX_BLOCK), 0, s, ro_l, ci_l, va_l, einv_s, rows,
-                       count, rhs, w);
+    DILU_LANES_LAUNCH(dilu_fwd_scalar_lower, lanes, count, s, ro_l, ci_l,
+                      va_l, einv_s, rows, count, rhs, w);
 }
 
 template <typename TA, typename TV>
 void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
                     const TA* einv_s, const int* rows, int count, TV* w,
-                    TV* x, TV relax, hipStream_t s) {
+                    TV* x, TV relax, int lanes, hipStream_t s) {
     if (count <= 0) return;
-    hipLaunchKernelGGL((dilu_bwd_scalar_upper<TA, TV>), dim3(grid_1d(count)),
-                       dim3(AMGX_BLOCK), 0, s, ro_u, ci_u, va_u, einv_s, rows,
-                       count, w, x, relax);
+    DILU_LANES_LAUNCH(dilu_bwd_scalar_upper, lanes, count, s, ro_u, ci_u,
+                      va_u, einv_s, rows, count, w, x, relax);
 }
+#undef DILU_LANES_LAUNCH
 
 // ============================================================ transfers
 template <typename T>
@@ -1168,6 +1264,7 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
     AMGX_INSTANTIATE(extract_diag, T)                                           \
     AMGX_INSTANTIATE(jacobi_dinv, T)                                            \
     AMGX_INSTANTIATE(dilu_setup_color, T)                                       \
+    AMGX_INSTANTIATE(dilu_y_init, T)                                            \
     AMGX_INSTANTIATE(restrict_agg, T)                                           \
     AMGX_INSTANTIATE(restrict_csr, T)                                           \
     AMGX_INSTANTIATE(prolongate_agg, T)                                         \
@@ -1181,6 +1278,7 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
     AMGX_INSTANTIATE(dilu_small, TA, TV)                                        \
     AMGX_INSTANTIATE(dilu_fwd_sorted, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_bwd_sorted, TA, TV)                                   \
+    AMGX_INSTANTIATE(dilu_fwd_full, TA, TV)                                     \
     AMGX_INSTANTIATE(dilu_fwd_lower, TA, TV)                                    \
     AMGX_INSTANTIATE(dilu_bwd_upper, TA, TV)                                    \
     AMGX_INSTANTIATE(gs_sweep_small, TA, TV)                                    \

@@ -350,14 +350,16 @@ def _gather_part(va_s, part):
     return out
 
 
-def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused):
+def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0):
     n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
     w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
     st = _slabs(A, coloring)
     if _split_path(A):
         ro_u, ci_u, _ = _slab_part(st, True)
+        y = None
         if fused:
             fwd = (st.ro_s, st.ci_s, Einv.va_s)
+            y = _scratch(A, "dilu_y", n, x.dtype)   # x + w, the gathered one
         else:
             ro_l, ci_l, _ = part = _slab_part(st, False)
             if Einv.va_l is None:
@@ -366,8 +368,11 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused):
         _core.dilu_split(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
                          coloring.rows_sorted, coloring.bounds,
                          rhs.reshape(-1), w, x.reshape(-1),
-                         float(relaxation), fused)
+                         float(relaxation), fused, int(lanes), y)
         return
+    if lanes:
+        raise ValueError("lanes selects the form of the scalar per-color "
+                         "sweeps; this level does not run them")
     z = _scratch(A, "dilu_z", n, x.dtype)
     _core.dilu_sorted(st.ro_s, st.ci_s, Einv.va_s, A.block_dim, Einv.einv_s,
                       coloring.rows_sorted, coloring.bounds,
@@ -375,21 +380,23 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused):
                       x.reshape(-1), float(relaxation), fused)
 
 
-def dilu_smooth(A, Einv, coloring, b, x, relaxation):
+def dilu_smooth(A, Einv, coloring, b, x, relaxation, lanes=0):
     """x += relax * M^{-1}(b - A x) with the residual fused into the
     forward sweep (one matrix read fewer than residual + dilu_solve);
     b=1 scalar and b=4 MFMA paths. Returns False when this block size has
-    no fused kernel (caller falls back to residual + dilu_solve)."""
+    no fused kernel (caller falls back to residual + dilu_solve).
+    lanes (tests, bench_kernels.py): lanes per row of the scalar per-color
+    sweeps, 1 or 8; 0 routes each slab by its entries per row."""
     if A.block_dim not in (1, 4):
         return False
     if getattr(A, "manager", None) is not None:
         return False   # distributed path must exchange halos of x first
-    _dilu_sorted(A, Einv, coloring, b, x, relaxation, True)
+    _dilu_sorted(A, Einv, coloring, b, x, relaxation, True, lanes)
     return True
 
 
-def dilu_solve(A, Einv, coloring, r, relaxation, x):
-    _dilu_sorted(A, Einv, coloring, r, x, relaxation, False)
+def dilu_solve(A, Einv, coloring, r, relaxation, x, lanes=0):
+    _dilu_sorted(A, Einv, coloring, r, x, relaxation, False, lanes)
     return x
 
 

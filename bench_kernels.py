@@ -8,6 +8,7 @@ against the analytic bytes-moved model. One JSON line per kernel to stdout;
 human table to stderr.
 
     python bench_kernels.py [--size 192] [--iters 20] [--section multi_pairwise]
+    python bench_kernels.py [--size 192] [--iters 20] [--section dilu_lanes]
 """
 
 import argparse
@@ -85,13 +86,76 @@ def propose_records(A, tag, iters, sync, rec):
             sizes = level_sizes
 
 
+def bench_dilu_lanes(A, iters, sync, rec):
+    """The three scalar per-color DILU sweeps with 1 and 8 lanes per row on
+    the 7-point matrix and on its first two Galerkin levels under SIZE_2
+    aggregation (about 7, 10 and 12.7 entries per row). A sweep is timed
+    through one apply whose other sweep runs over an empty slab; `base` is
+    the apply with both slabs empty (launches and row traffic only), to be
+    subtracted. The whole fused and plain applies follow."""
+    from amgx_amd import _core, ops
+    from amgx_amd.amg.coloring import MatrixColoring
+    from amgx_amd.config import ConfigScope
+    from amgx_amd.ops import gpu as G
+
+    for level in range(3):
+        if level:
+            agg, num = ops.size2_matching(A)
+            A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
+        n, nnz = A.n_rows, A.nnz
+        if n <= _core.SMALL_LEVEL_ROWS:
+            sys.exit("--section dilu_lanes: level too small for the "
+                     "per-color path; raise --size")
+        col = MatrixColoring.create(A, ConfigScope(None, {}))
+        einv = ops.dilu_setup(A, col)
+        st = G._slabs(A, col)
+        ro_u, ci_u, _ = G._slab_part(st, True)
+        ro_l, ci_l, _ = part_l = G._slab_part(st, False)
+        va_l = G._gather_part(einv.va_s, part_l)
+        ro_0 = torch.zeros_like(ro_u)
+        ci_0, va_0 = ci_u[:0], einv.va_u[:0]
+        b = torch.ones(A.n_cols, dtype=torch.float64, device=A.device)
+        x = torch.zeros_like(b)
+        w, y = torch.empty_like(b), torch.empty_like(b)
+        full = (st.ro_s, st.ci_s, einv.va_s)
+        lower, upper = (ro_l, ci_l, va_l), (ro_u, ci_u, einv.va_u)
+        empty = (ro_0, ci_0, va_0)
+        # bytes: offsets + rows_sorted + Einv per sweep, then the row's own
+        # reads and writes (bench_kernels.py main, dilu records)
+        sweep = n * 16 + 4
+        cases = (("base", empty, empty, False, None),
+                 ("fwd_full", full, empty, True, nnz * 12 + sweep + n * 40),
+                 ("fwd_lower", lower, empty, False,
+                  ci_l.numel() * 12 + sweep + n * 24),
+                 ("bwd_upper", empty, upper, False,
+                  ci_u.numel() * 12 + sweep + n * 32))
+        print(f"level {level}: {n} rows, {nnz / n:.2f} entries/row "
+              f"(L {ci_l.numel() / n:.2f}, U {ci_u.numel() / n:.2f}), "
+              f"{col.num_colors} colors", file=sys.stderr)
+        for name, fwd, bwd, fused, nbytes in cases:
+            for lanes in (1, 8):
+                sec = bench(lambda: _core.dilu_split(
+                    *fwd, *bwd, einv.einv_s, col.rows_sorted, col.bounds, b,
+                    w, x, 0.75, fused, lanes, y), iters, sync)
+                rec(f"dilu_{name}_g{level}_l{lanes}", sec, nbytes,
+                    entries_per_row=nnz / n)
+        for lanes in (0, 1, 8):
+            rec(f"dilu_smooth_g{level}_l{lanes}", bench(
+                lambda: G.dilu_smooth(A, einv, col, b, x, 0.75, lanes=lanes),
+                iters, sync), entries_per_row=nnz / n)
+            rec(f"dilu_apply_g{level}_l{lanes}", bench(
+                lambda: G.dilu_solve(A, einv, col, b, 0.75, x, lanes=lanes),
+                iters, sync), entries_per_row=nnz / n)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=192)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--section", default="all",
-                    choices=("all", "multi_pairwise"),
-                    help="multi_pairwise: only the MULTI_PAIRWISE records")
+                    choices=("all", "multi_pairwise", "dilu_lanes"),
+                    help="multi_pairwise: only the MULTI_PAIRWISE records; "
+                         "dilu_lanes: the DILU sweeps by lanes per row")
     args = ap.parse_args()
     sys.path.insert(0, ".")
     from amgx_amd import ops
@@ -114,15 +178,21 @@ def main():
 
     results = {}
 
-    def rec(name, sec, bytes_moved=None):
+    def rec(name, sec, bytes_moved=None, **extra):
         gbps = bytes_moved / sec / 1e9 if bytes_moved else None
         results[name] = {"ms": sec * 1e3, "GBps": gbps}
-        print(json.dumps({"kernel": name, "ms": sec * 1e3, "GBps": gbps}))
+        print(json.dumps({"kernel": name, "ms": sec * 1e3, "GBps": gbps,
+                          **extra}))
 
     if args.section == "multi_pairwise":
         if dev == "cpu":
             sys.exit("--section multi_pairwise times device kernels: no GPU")
         bench_multi_pairwise(A, args.iters, sync, rec)
+        return
+    if args.section == "dilu_lanes":
+        if dev == "cpu":
+            sys.exit("--section dilu_lanes times device kernels: no GPU")
+        bench_dilu_lanes(A, args.iters, sync, rec)
         return
 
     rec("csrmv", bench(lambda: ops.spmv(A, x, y), args.iters, sync),
@@ -166,8 +236,8 @@ def main():
     # Both sweeps read offsets + rows_sorted + Einv (n * 16 + 4); the
     # backward sweep reads the U part, reads and writes w and x (n * 32).
     # dilu_apply: forward over the L part, reads r and w, writes w (n * 24).
-    # dilu_smooth: w memset (n * 8), forward over the full slab, reads b, x
-    # and w, writes w (n * 32).
+    # dilu_smooth: the y = x + 0 pass (n * 16), forward over the full slab,
+    # reads b, x and the one gathered vector y, writes w and y (n * 40).
     st = A._cache.get("slabs")
     if st is not None and getattr(st, "upper", None) is not None:
         nnz_u = st.upper[1].numel()
@@ -180,7 +250,7 @@ def main():
     if getattr(B, "dilu_smooth", None) is not None:
         rec("dilu_smooth", bench(
             lambda: B.dilu_smooth(A, einv, col, b, y, 0.75), args.iters,
-            sync), n * 8 + nnz * 12 + sweep_bytes + n * 32 + bwd_bytes)
+            sync), n * 16 + nnz * 12 + sweep_bytes + n * 40 + bwd_bytes)
 
     # block-4 kernels: MFMA wave path vs the scalar baseline
     from amgx_amd.problems import block_laplacian
