@@ -62,9 +62,16 @@ __device__ __forceinline__ unsigned int hash_col(int c) {
 
 // hash-SET insert (count pass): returns +1 if newly inserted, 0 if present,
 // -1 on table-full overflow.
+//
+// Probe budget of hset_insert and hmap_add: `visited` counts the slots a key
+// has moved past, not loop iterations. A lane that loses the CAS for an empty
+// slot to another key looks at the same slot again, finds it occupied and
+// moves on; that retry costs no budget. A key therefore gives up only after
+// it has seen all cap slots occupied by other keys, so a row whose distinct
+// keys fit the table cannot fail, however many lanes insert at once.
 __device__ __forceinline__ int hset_insert(int* keys, int cap, int key) {
     unsigned int h = hash_col(key) & (cap - 1);
-    for (int probe = 0; probe < cap; ++probe) {
+    for (int visited = 0; visited < cap;) {
         int k0 = keys[h];
         if (k0 == key) return 0;
         if (k0 == -1) {
@@ -74,6 +81,7 @@ __device__ __forceinline__ int hset_insert(int* keys, int cap, int key) {
             continue;      // slot stolen by another key: retry same slot
         }
         h = (h + 1) & (cap - 1);
+        ++visited;
     }
     return -1;
 }
@@ -85,7 +93,7 @@ template <typename T>
 __device__ __forceinline__ bool hmap_add(int* keys, T* vals, int cap,
                                          int key, T v) {
     unsigned int h = hash_col(key) & (cap - 1);
-    for (int probe = 0; probe < cap; ++probe) {
+    for (int visited = 0; visited < cap;) {
         int k0 = keys[h];
         if (k0 == key) { atomicAdd(&vals[h], v); return true; }
         if (k0 == -1) {
@@ -94,9 +102,10 @@ __device__ __forceinline__ bool hmap_add(int* keys, T* vals, int cap,
                 atomicAdd(&vals[h], v);
                 return true;
             }
-            continue;
+            continue;      // slot stolen by another key: retry same slot
         }
         h = (h + 1) & (cap - 1);
+        ++visited;
     }
     return false;
 }
@@ -209,6 +218,9 @@ __global__ __launch_bounds__(64 * WAVES) void spgemm_count_kernel(
 // ============================================================ fill pass
 // Writes each row's (col, val) entries sorted by column.  SORTED=0 keeps
 // the unsorted hash order (the Python caller sorts the rare huge rows).
+// hmap_add's return value is not checked: the row guard admits only rows
+// whose counted width fits CAP, and under the slots-visited probe budget
+// (hset_insert) such a row cannot fail to insert.
 template <typename T, int CAP, int WAVES, int SORTED>
 __global__ __launch_bounds__(64 * WAVES) void spgemm_fill_kernel(
     const int* __restrict__ roA, const int* __restrict__ ciA,
@@ -297,6 +309,12 @@ long long spgemm_hash(const int* roA, const int* ciA, const T* vaA, int m,
                       int* ciC_cap_buf, T* vaC_cap_buf, long long cap_nnz,
                       int** big_rows_out, int* n_big_out, hipStream_t s) {
     constexpr int BIG_CAP = spgemm_hash_top_cap<T>();
+    if (m == 0) {       // no rows: the empty product, no 0-block launches
+        HIP_CHECK(hipMemsetAsync(roC_out, 0, sizeof(int), s));
+        *big_rows_out = nullptr;
+        *n_big_out = 0;
+        return 0;
+    }
     int* counts = nullptr;
     HIP_CHECK(hipMallocAsync(&counts, (m + 1) * sizeof(int), s));
     int* ovf = nullptr;
@@ -498,6 +516,8 @@ __global__ __launch_bounds__(64 * WAVES) void ilu1_count_kernel(
 
 // Writes each row's columns ascending (the factor kernels binary-search
 // them).  SORTED=0 keeps the hash order; the caller sorts those rows.
+// ovf is not looked at here: count <= CAP, so every insert finds its slot
+// (the probe budget of hset_insert).
 template <int CAP, int WAVES, int SORTED>
 __global__ __launch_bounds__(64 * WAVES) void ilu1_fill_kernel(
     const int* __restrict__ ro, const int* __restrict__ ci,
