@@ -492,26 +492,32 @@ std::vector<Tensor> slab_split(Tensor ro_s, Tensor ci_s, Tensor rows_sorted,
 // fused: rhs is b and the residual b - A x is folded into the forward
 // sweep (one matrix read fewer per smoother iteration than residual
 // kernel + apply); scalar and block-4 only.
-// Block matrices and small scalar levels; scalar levels past
-// SMALL_LEVEL_ROWS run dilu_split.
+// Block matrices. Scalar levels run dilu_small up to DILU_SMALL_ROWS rows
+// and dilu_split past it; a scalar call here is the one-launch apply in its
+// earlier full-slab form (dilu_small_full), which tests and bench_kernels.py
+// compare against, with any_size lifting the row bound for the latter.
 void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
                  Tensor einv_s, Tensor rows_sorted,
                  std::vector<int64_t> bounds, Tensor bounds_dev, Tensor rhs,
-                 Tensor w, Tensor z, Tensor x, double relax, bool fused) {
+                 Tensor w, Tensor z, Tensor x, double relax, bool fused,
+                 bool any_size) {
     TORCH_CHECK(!fused || b == 1 || b == 4,
                 "dilu_sorted: no fused-residual kernel for block_dim ", b);
     check_scalar_if_complex(va_s, b, "dilu_sorted");
     int nc = (int)bounds.size() - 1;
     int bb = (int)(b * b);
     int64_t n = (int64_t)ro_s.numel() - 1;
-    // small levels: ONE fused single-WG launch for the whole apply
-    // (zeroing + all colors both sweeps + relaxed axpy)
     if (b == 1) {
-        TORCH_CHECK(n <= amgx_hip::SMALL_LEVEL_ROWS,
+        TORCH_CHECK(any_size || n <= amgx_hip::DILU_SMALL_ROWS,
                     "dilu_sorted: scalar levels of more than ",
-                    amgx_hip::SMALL_LEVEL_ROWS, " rows run dilu_split");
-        DISPATCH(AMGX_VALUE_PAIRS, "dilu_small", (va_s, x), [&] {
-            amgx_hip::dilu_small<scalar_a, scalar_v>(
+                    amgx_hip::DILU_SMALL_ROWS, " rows run dilu_split");
+        TORCH_CHECK(bounds_dev.numel() == nc + 1 && rows_sorted.numel() == n &&
+                        w.numel() >= n && z.numel() >= w.numel() &&
+                        x.numel() >= n && rhs.numel() >= n &&
+                        (!fused || x.numel() >= w.numel()),
+                    "dilu_sorted: vectors shorter than the matrix");
+        DISPATCH(AMGX_VALUE_PAIRS, "dilu_small_full", (va_s, x), [&] {
+            amgx_hip::dilu_small_full<scalar_a, scalar_v>(
                 iptr(ro_s), iptr(ci_s), dptr<scalar_a>(va_s),
                 dptr<scalar_a>(einv_s), iptr(rows_sorted), iptr(bounds_dev),
                 nc, dptr<scalar_v>(rhs), dptr<scalar_v>(w), dptr<scalar_v>(z),
@@ -634,6 +640,72 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                 (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(x),
                 (scalar_v)relax, lanes_u, st);
         });
+    });
+}
+
+// one-launch scalar DILU apply for small levels: `sweeps` applies of
+// x += relax * M^{-1} rhs back to back in one single-workgroup launch, the
+// same arguments and the same bits as `sweeps` calls of dilu_split (bounds
+// also as the device copy bounds_dev, which the kernel reads). y is required
+// when fused; nothing is allocated, so the call is capturable in a hipGraph.
+// Levels of at most DILU_SMALL_ROWS rows; any_size (tests, bench_kernels.py)
+// lifts that bound. lanes as in dilu_split.
+void dilu_small(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
+                Tensor ci_u, Tensor va_u, Tensor einv_s, Tensor rows_sorted,
+                std::vector<int64_t> bounds, Tensor bounds_dev, Tensor rhs,
+                Tensor w, Tensor x, double relax, bool fused, int64_t lanes,
+                c10::optional<Tensor> y_opt, int64_t sweeps, bool any_size) {
+    int64_t n = (int64_t)ro_u.numel() - 1;
+    int64_t nc = (int64_t)bounds.size() - 1;
+    TORCH_CHECK(any_size || n <= amgx_hip::DILU_SMALL_ROWS,
+                "dilu_small: scalar levels of more than ",
+                amgx_hip::DILU_SMALL_ROWS, " rows run dilu_split");
+    TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
+                    einv_s.numel() == n,
+                "dilu_small: slabs, rows_sorted and Einv disagree on n");
+    TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n &&
+                    bounds_dev.numel() == nc + 1 &&
+                    bounds_dev.scalar_type() == torch::kInt32,
+                "dilu_small: color bounds do not cover the n rows");
+    TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
+                "dilu_small: scalar slabs hold one value per column index");
+    TORCH_CHECK(rhs.numel() >= n && x.numel() >= n && w.numel() >= n &&
+                    (!fused || w.numel() >= x.numel()),
+                "dilu_small: vectors shorter than the matrix");
+    TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
+                    rhs.scalar_type() == x.scalar_type() &&
+                    va_u.scalar_type() == va_f.scalar_type() &&
+                    einv_s.scalar_type() == va_f.scalar_type(),
+                "dilu_small: mixed value types");
+    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
+                "dilu_small: lanes must be 0 (routed), 1 or 8");
+    TORCH_CHECK(sweeps >= 1 && sweeps <= (1 << 20),
+                "dilu_small: sweeps must be at least 1");
+    for (Tensor t : {ro_f, ci_f, va_f, ro_u, ci_u, va_u, einv_s, rows_sorted,
+                     bounds_dev, rhs, w, x})
+        check_dev(t);
+    Tensor y;
+    if (fused) {
+        TORCH_CHECK(y_opt.has_value(), "dilu_small: a fused apply needs y");
+        y = *y_opt;
+        TORCH_CHECK(y.is_contiguous() && y.device() == x.device() &&
+                        y.scalar_type() == x.scalar_type() &&
+                        y.numel() >= x.numel(),
+                    "dilu_small: y must be a vector like w");
+    }
+    double rows = (double)std::max<int64_t>(n, 1);
+    int lanes_f = lanes ? (int)lanes
+                        : (int)dilu_lanes((double)ci_f.numel() / rows, !fused);
+    int lanes_u = lanes ? (int)lanes
+                        : (int)dilu_lanes((double)ci_u.numel() / rows, true);
+    DISPATCH(AMGX_VALUE_PAIRS, "dilu_small", (va_f, x), [&] {
+        amgx_hip::dilu_small<scalar_a, scalar_v>(
+            iptr(ro_f), iptr(ci_f), dptr<scalar_a>(va_f), iptr(ro_u),
+            iptr(ci_u), dptr<scalar_a>(va_u), dptr<scalar_a>(einv_s),
+            iptr(rows_sorted), iptr(bounds_dev), (int)nc, dptr<scalar_v>(rhs),
+            dptr<scalar_v>(w), fused ? dptr<scalar_v>(y) : nullptr,
+            dptr<scalar_v>(x), (scalar_v)relax, (long long)x.numel(), fused,
+            lanes_f, lanes_u, (int)sweeps, cur_stream());
     });
 }
 
@@ -1154,7 +1226,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gs_sweep", &gs_sweep);
     m.def("gs_sweep_sorted", &gs_sweep_sorted);
     m.def("dilu_setup", &dilu_setup);
-    m.def("dilu_sorted", &dilu_sorted);
+    // row bound of the one-launch scalar DILU apply (dilu_small)
+    m.attr("DILU_SMALL_ROWS") = amgx_hip::DILU_SMALL_ROWS;
+    {   // any_size is optional: 14 positional arguments still work
+        using pybind11::arg;
+        m.def("dilu_sorted", &dilu_sorted, arg("ro_s"), arg("ci_s"),
+              arg("va_s"), arg("b"), arg("einv_s"), arg("rows_sorted"),
+              arg("bounds"), arg("bounds_dev"), arg("rhs"), arg("w"),
+              arg("z"), arg("x"), arg("relax"), arg("fused"),
+              arg("any_size") = false);
+        m.def("dilu_small", &dilu_small, arg("ro_f"), arg("ci_f"),
+              arg("va_f"), arg("ro_u"), arg("ci_u"), arg("va_u"),
+              arg("einv_s"), arg("rows_sorted"), arg("bounds"),
+              arg("bounds_dev"), arg("rhs"), arg("w"), arg("x"), arg("relax"),
+              arg("fused"), arg("lanes") = 0, arg("y") = pybind11::none(),
+              arg("sweeps") = 1, arg("any_size") = false);
+    }
     {   // trailing lanes / y are optional: 14 positional arguments still work
         using pybind11::arg;
         m.def("dilu_split", &dilu_split, arg("ro_f"), arg("ci_f"),

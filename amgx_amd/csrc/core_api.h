@@ -111,9 +111,10 @@ void gs_smooth_rows(const int* ro, const int* ci, const TA* va,
 
 // ---- color-sorted sweeps (reorder-by-color layout) -------------------------
 // Matrix arrays are the rows_sorted-gathered copy, so each color reads one
-// contiguous slab. Levels of at most SMALL_LEVEL_ROWS rows run the whole
-// sweep in one single-workgroup launch (*_small); larger levels launch once
-// per color with ro_s/rows/dinv_s/einv_s pre-offset to the color base.
+// contiguous slab. Levels of at most SMALL_LEVEL_ROWS rows (GS) or
+// DILU_SMALL_ROWS rows (scalar DILU) run the whole sweep in one
+// single-workgroup launch (*_small); larger levels launch once per color
+// with ro_s/rows/dinv_s/einv_s pre-offset to the color base.
 // All [value]; Einv is held in the matrix type.
 constexpr int SMALL_LEVEL_ROWS = 1 << 14;
 
@@ -130,13 +131,34 @@ void gs_rows_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
 // DILU: x += relax * M^{-1} rhs.  Fused-residual form: rhs = b and the
 // forward sweep folds the residual in, so M^{-1}(b - A x) costs one matrix
 // read less; scalar and block-4 only.
-// whole apply for small scalar levels: zeroing, all forward colors, all
-// backward colors and the relaxed axpy
+// `sweeps` whole applies for a small scalar level in one single-workgroup
+// launch, with the arithmetic (and bits) of the per-color kernels below:
+// fused sweeps the full slab (ro_f, ci_f, va_f) gathering y = x + w, with
+// y = x + 0 over vec_n entries written by the kernel at each apply; plain
+// sweeps the L slab (same arguments, y unused) gathering w; backward over U in
+// place in w with x += relax z folded in. w and y need no zeroing. lanes_f /
+// lanes_u: 1 or 8 lanes per row of the forward / backward slab.
+// Levels of at most DILU_SMALL_ROWS rows take it; the boundary is the
+// measured crossover with the per-color path, whose three sweeps cost about
+// the same 0.3 ms of launches from 1400 to 27000 rows while one workgroup's
+// time grows with the rows (profiles/NOTES.md, "DILU one-launch apply of
+// small levels").
+constexpr int DILU_SMALL_ROWS = 1 << 10;
 template <typename TA, typename TV>
-void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
+void dilu_small(const int* ro_f, const int* ci_f, const TA* va_f,
+                const int* ro_u, const int* ci_u, const TA* va_u,
                 const TA* einv_s, const int* rows, const int* bounds,
-                int ncolors, const TV* rhs, TV* w, TV* z, TV* x, TV relax,
-                long long vec_n, bool fused, hipStream_t s);
+                int ncolors, const TV* rhs, TV* w, TV* y, TV* x, TV relax,
+                long long vec_n, bool fused, int lanes_f, int lanes_u,
+                int sweeps, hipStream_t s);
+// the one-launch apply in its earlier form, for tests and bench_kernels.py:
+// thread per row over the full slab in both sweeps, w and z zeroed at each
+// apply, the relaxed axpy a pass of its own. Same bits as dilu_small.
+template <typename TA, typename TV>
+void dilu_small_full(const int* ro_s, const int* ci_s, const TA* va_s,
+                     const TA* einv_s, const int* rows, const int* bounds,
+                     int ncolors, const TV* rhs, TV* w, TV* z, TV* x,
+                     TV relax, long long vec_n, bool fused, hipStream_t s);
 // block matrices only; xres (block-4) folds the residual in by gathering
 // xres + w over a pre-zeroed w
 template <typename TA, typename TV>

@@ -974,15 +974,105 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_block_sorted(
     }
 }
 
-// Whole-apply fused kernel for SMALL levels (the deep AMG tail): ONE
-// single-workgroup launch runs zeroing, every forward color, every
-// backward color and the relaxed axpy, with __syncthreads as the color
-// barrier.  The per-color launch floor (~5-20us x ncolors x 2 sweeps x
-// sweeps-per-smooth x ~15 coarse levels) dominated the V-cycle before
-// this (rocprof r02: 95k launches, 2.0 of 3.0 s GPU time at 192^3).
-// FUSED: rhs is b and the forward gather is x[j]+w[j] (fused residual).
-template <typename TA, typename TV, bool FUSED>
+// One-launch DILU apply for small scalar levels (the deep AMG tail): ONE
+// single-workgroup launch runs `sweeps` whole applies back to back, every
+// forward and backward color of each, with __syncthreads as the color
+// barrier, where the per-color path pays 2 x colors + 1 launches per apply.
+// The arithmetic is that of the per-color kernels above, expression for
+// expression, so the two paths give the same bits: FUSED sweeps the full
+// slab (ro_f, ci_f, va_f) gathering the one vector y = x + w, which the
+// kernel itself rewrites as y = x + 0 at the start of every apply; plain
+// sweeps the L slab (same three arguments) gathering w. The backward sweep
+// runs over the U slab in place in w and carries x_i += relax z_i. Neither w
+// nor y is read before this launch has written it.
+// LF / LU lanes per row of the forward / backward slab (slab_row_dot_lanes).
+// A color takes ceil(rows * LANES / blockDim) rounds; blockDim is a multiple
+// of LANES, so the lanes of a row share a round, and no thread leaves a
+// color before its barrier.
+template <int LANES, typename TA, typename TV, typename RowOp>
+__device__ __forceinline__ void dilu_small_color(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const TA* __restrict__ va, const TV* v, int s0, int s1, RowOp row_op) {
+    const int lane = threadIdx.x & (LANES - 1);
+    const int per_round = blockDim.x / LANES;
+    for (int t0 = s0; t0 < s1; t0 += per_round) {
+        int t = t0 + threadIdx.x / LANES;
+        if (t < s1) {   // uniform over the lanes of a row
+            TV sum = slab_row_dot_lanes<LANES>(ro, ci, va, t, lane, v);
+            if (lane == 0) row_op(t, sum);
+        }
+    }
+    __syncthreads();
+}
+
+template <int LF, int LU, typename TA, typename TV, bool FUSED>
 __global__ __launch_bounds__(1024) void dilu_small_kernel(
+    const int* __restrict__ ro_f, const int* __restrict__ ci_f,
+    const TA* __restrict__ va_f, const int* __restrict__ ro_u,
+    const int* __restrict__ ci_u, const TA* __restrict__ va_u,
+    const TA* __restrict__ einv_s, const int* __restrict__ rows,
+    const int* __restrict__ bounds, int ncolors, const TV* __restrict__ rhs,
+    TV* w, TV* y, TV* x, TV relax, long long vec_n, int sweeps) {
+    for (int sw = 0; sw < sweeps; ++sw) {
+        if constexpr (FUSED) {
+            for (long long j = threadIdx.x; j < vec_n; j += blockDim.x)
+                y[j] = x[j] + TV(0);
+            __syncthreads();
+        }
+        for (int c = 0; c < ncolors; ++c) {
+            dilu_small_color<LF, TA, TV>(
+                ro_f, ci_f, va_f, FUSED ? y : w, bounds[c], bounds[c + 1],
+                [&](int t, TV sum) {
+                    int i = rows[t];
+                    TV wi = (TV)einv_s[t] * (rhs[i] - sum);
+                    w[i] = wi;
+                    if constexpr (FUSED) y[i] = add_unfused(x[i], wi);
+                });
+        }
+        for (int c = ncolors - 1; c >= 0; --c) {
+            dilu_small_color<LU, TA, TV>(
+                ro_u, ci_u, va_u, w, bounds[c], bounds[c + 1],
+                [&](int t, TV sum) {
+                    int i = rows[t];
+                    TV z = w[i] - (TV)einv_s[t] * sum;
+                    w[i] = z;
+                    x[i] += relax * z;
+                });
+        }
+    }
+}
+
+template <typename TA, typename TV>
+void dilu_small(const int* ro_f, const int* ci_f, const TA* va_f,
+                const int* ro_u, const int* ci_u, const TA* va_u,
+                const TA* einv_s, const int* rows, const int* bounds,
+                int ncolors, const TV* rhs, TV* w, TV* y, TV* x, TV relax,
+                long long vec_n, bool fused, int lanes_f, int lanes_u,
+                int sweeps, hipStream_t s) {
+    if ((lanes_f != 1 && lanes_f != 8) || (lanes_u != 1 && lanes_u != 8))
+        throw std::runtime_error("dilu_small: lanes must be 1 or 8");
+    if (sweeps <= 0) return;
+#define DILU_SMALL_FORM(LF, LU)                                                \
+    (fused ? dilu_small_kernel<LF, LU, TA, TV, true>                           \
+           : dilu_small_kernel<LF, LU, TA, TV, false>)
+    auto kern = lanes_f == 8
+                    ? (lanes_u == 8 ? DILU_SMALL_FORM(8, 8)
+                                    : DILU_SMALL_FORM(8, 1))
+                    : (lanes_u == 8 ? DILU_SMALL_FORM(1, 8)
+                                    : DILU_SMALL_FORM(1, 1));
+#undef DILU_SMALL_FORM
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, s, ro_f, ci_f, va_f,
+                       ro_u, ci_u, va_u, einv_s, rows, bounds, ncolors, rhs,
+                       w, y, x, relax, vec_n, sweeps);
+}
+
+// The one-launch apply as it was before the split slabs reached the small
+// levels, kept for tests and bench_kernels.py to compare against: thread per
+// row over the full slab in both sweeps, two gathered vectors in the fused
+// forward sweep, w and z zeroed at every apply and the relaxed axpy as a
+// pass of its own. Same bits as dilu_small: the extra terms are exact zeros.
+template <typename TA, typename TV, bool FUSED>
+__global__ __launch_bounds__(1024) void dilu_small_full_kernel(
     const int* __restrict__ ro_s, const int* __restrict__ ci_s,
     const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
     const int* __restrict__ rows, const int* __restrict__ bounds,
@@ -1021,12 +1111,12 @@ __global__ __launch_bounds__(1024) void dilu_small_kernel(
 }
 
 template <typename TA, typename TV>
-void dilu_small(const int* ro_s, const int* ci_s, const TA* va_s,
-                const TA* einv_s, const int* rows, const int* bounds,
-                int ncolors, const TV* rhs, TV* w, TV* z, TV* x, TV relax,
-                long long vec_n, bool fused, hipStream_t s) {
-    auto kern = fused ? dilu_small_kernel<TA, TV, true>
-                      : dilu_small_kernel<TA, TV, false>;
+void dilu_small_full(const int* ro_s, const int* ci_s, const TA* va_s,
+                     const TA* einv_s, const int* rows, const int* bounds,
+                     int ncolors, const TV* rhs, TV* w, TV* z, TV* x,
+                     TV relax, long long vec_n, bool fused, hipStream_t s) {
+    auto kern = fused ? dilu_small_full_kernel<TA, TV, true>
+                      : dilu_small_full_kernel<TA, TV, false>;
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, s, ro_s, ci_s, va_s,
                        einv_s, rows, bounds, ncolors, rhs, w, z, x, relax,
                        vec_n);
@@ -1276,6 +1366,7 @@ void gather(const T* src, const int* idx, int count, int b, T* dst,
     AMGX_INSTANTIATE(csrmv, TA, TV)                                             \
     AMGX_INSTANTIATE(jacobi_smooth, TA, TV)                                     \
     AMGX_INSTANTIATE(dilu_small, TA, TV)                                        \
+    AMGX_INSTANTIATE(dilu_small_full, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_fwd_sorted, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_bwd_sorted, TA, TV)                                   \
     AMGX_INSTANTIATE(dilu_fwd_full, TA, TV)                                     \

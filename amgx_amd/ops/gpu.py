@@ -285,15 +285,16 @@ def _slab_part(st, upper):
 
 
 def _split_path(A):
-    """Scalar levels past the single-workgroup size sweep the split slabs."""
-    return A.block_dim == 1 and A.n_rows > _core.SMALL_LEVEL_ROWS
+    """Scalar levels past the size of the one-launch apply sweep the split
+    slabs color by color."""
+    return A.block_dim == 1 and A.n_rows > _core.DILU_SMALL_ROWS
 
 
 class DiluState:
     """Device DILU factor state: Einv in original row order (einv) plus the
-    color-sorted matrix/Einv copies the sweeps read contiguously. On the
-    split-slab path va_u holds the values of the U part and va_l, gathered
-    on the first plain apply, those of the L part."""
+    color-sorted matrix/Einv copies the sweeps read contiguously. For scalar
+    matrices va_u holds the values of the U part and va_l, gathered on the
+    first plain apply, those of the L part."""
     __slots__ = ("einv", "va_s", "einv_s", "va_u", "va_l")
 
     def __init__(self, einv, va_s, einv_s, va_u=None):
@@ -339,7 +340,8 @@ def dilu_setup(A, coloring):
     va_s = A.values.reshape(A.nnz, -1)[st.nzmap].reshape(-1).contiguous()
     einv_s = einv.reshape(A.n_rows, bb)[st.perm].reshape(-1).contiguous() \
         if A.block_dim > 1 else einv[st.perm].contiguous()
-    va_u = _gather_part(va_s, _slab_part(st, True)) if _split_path(A) \
+    # scalar levels of every size sweep the U part backwards
+    va_u = _gather_part(va_s, _slab_part(st, True)) if A.block_dim == 1 \
         else None
     return DiluState(einv, va_s, einv_s, va_u)
 
@@ -350,11 +352,30 @@ def _gather_part(va_s, part):
     return out
 
 
-def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0):
+DILU_FORMS = ("split", "small", "small_full")
+
+
+def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
+                 sweeps=1, form=None):
+    """`sweeps` applies back to back. Scalar levels take the one-launch apply
+    ("small") up to DILU_SMALL_ROWS rows and the per-color sweeps ("split")
+    past it; form (tests, bench_kernels.py) names one of DILU_FORMS whatever
+    the size, "small_full" being the one-launch apply in its earlier
+    full-slab form."""
     n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
     w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
     st = _slabs(A, coloring)
-    if _split_path(A):
+    forced = form is not None     # lifts the row bound of the one-launch forms
+    if A.block_dim != 1:
+        if lanes or forced:
+            raise ValueError("lanes and form select among the scalar DILU "
+                             "sweeps; a block level does not run them")
+        form = "block"
+    elif form is None:
+        form = "split" if _split_path(A) else "small"
+    elif form not in DILU_FORMS:
+        raise ValueError(f"form must be one of {DILU_FORMS}")
+    if form in ("split", "small"):
         ro_u, ci_u, _ = _slab_part(st, True)
         y = None
         if fused:
@@ -365,38 +386,54 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0):
             if Einv.va_l is None:
                 Einv.va_l = _gather_part(Einv.va_s, part)
             fwd = (ro_l, ci_l, Einv.va_l)
-        _core.dilu_split(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
-                         coloring.rows_sorted, coloring.bounds,
-                         rhs.reshape(-1), w, x.reshape(-1),
-                         float(relaxation), fused, int(lanes), y)
+        if form == "small":
+            _core.dilu_small(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
+                             coloring.rows_sorted, coloring.bounds,
+                             coloring.bounds_dev, rhs.reshape(-1), w,
+                             x.reshape(-1), float(relaxation), fused,
+                             int(lanes), y, int(sweeps), forced)
+            return
+        for _ in range(sweeps):
+            _core.dilu_split(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
+                             coloring.rows_sorted, coloring.bounds,
+                             rhs.reshape(-1), w, x.reshape(-1),
+                             float(relaxation), fused, int(lanes), y)
         return
     if lanes:
-        raise ValueError("lanes selects the form of the scalar per-color "
-                         "sweeps; this level does not run them")
+        raise ValueError("lanes selects the form of the split-slab sweeps; "
+                         "the full-slab apply has one")
     z = _scratch(A, "dilu_z", n, x.dtype)
-    _core.dilu_sorted(st.ro_s, st.ci_s, Einv.va_s, A.block_dim, Einv.einv_s,
-                      coloring.rows_sorted, coloring.bounds,
-                      coloring.bounds_dev, rhs.reshape(-1), w, z,
-                      x.reshape(-1), float(relaxation), fused)
+    for _ in range(sweeps):
+        _core.dilu_sorted(st.ro_s, st.ci_s, Einv.va_s, A.block_dim,
+                          Einv.einv_s, coloring.rows_sorted, coloring.bounds,
+                          coloring.bounds_dev, rhs.reshape(-1), w, z,
+                          x.reshape(-1), float(relaxation), fused, forced)
 
 
-def dilu_smooth(A, Einv, coloring, b, x, relaxation, lanes=0):
+def dilu_smooth(A, Einv, coloring, b, x, relaxation, lanes=0, sweeps=1,
+                form=None):
     """x += relax * M^{-1}(b - A x) with the residual fused into the
     forward sweep (one matrix read fewer than residual + dilu_solve);
     b=1 scalar and b=4 MFMA paths. Returns False when this block size has
     no fused kernel (caller falls back to residual + dilu_solve).
-    lanes (tests, bench_kernels.py): lanes per row of the scalar per-color
-    sweeps, 1 or 8; 0 routes each slab by its entries per row."""
+    sweeps: that many smoothing steps back to back, in one launch where the
+    level takes the one-launch apply; the same bits as that many calls.
+    lanes (tests, bench_kernels.py): lanes per row of the scalar split-slab
+    sweeps, 1 or 8; 0 routes each slab by its entries per row. form: see
+    _dilu_sorted."""
     if A.block_dim not in (1, 4):
         return False
     if getattr(A, "manager", None) is not None:
         return False   # distributed path must exchange halos of x first
-    _dilu_sorted(A, Einv, coloring, b, x, relaxation, True, lanes)
+    _dilu_sorted(A, Einv, coloring, b, x, relaxation, True, lanes, sweeps,
+                 form)
     return True
 
 
-def dilu_solve(A, Einv, coloring, r, relaxation, x, lanes=0):
-    _dilu_sorted(A, Einv, coloring, r, x, relaxation, False, lanes)
+def dilu_solve(A, Einv, coloring, r, relaxation, x, lanes=0, sweeps=1,
+               form=None):
+    _dilu_sorted(A, Einv, coloring, r, x, relaxation, False, lanes, sweeps,
+                 form)
     return x
 
 

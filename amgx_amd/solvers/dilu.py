@@ -44,6 +44,17 @@ class MulticolorDILUSolver(_SmootherBase):
             A.coloring = MatrixColoring.create(A, self.scope)
         self.Einv = dilu_setup(A, A.coloring)
 
+    def sweep(self, b, x, n: int = 1):
+        # the backend's fused smoother takes the count: levels on the
+        # one-launch apply run all n sweeps in a single launch
+        B = ops._backend(self.A)
+        fused = getattr(B, "dilu_smooth", None)
+        if n > 1 and fused is not None and fused(
+                self.A, self.Einv, self.A.coloring, b, x,
+                self.relaxation_factor, sweeps=n):
+            return
+        super().sweep(b, x, n)
+
     def solve_iteration(self, b, x):
         B = ops._backend(self.A)
         fused = getattr(B, "dilu_smooth", None)

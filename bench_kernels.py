@@ -9,6 +9,7 @@ human table to stderr.
 
     python bench_kernels.py [--size 192] [--iters 20] [--section multi_pairwise]
     python bench_kernels.py [--size 192] [--iters 20] [--section dilu_lanes]
+    python bench_kernels.py --size 64 --iters 50 --section dilu_small
 """
 
 import argparse
@@ -103,7 +104,7 @@ def bench_dilu_lanes(A, iters, sync, rec):
             agg, num = ops.size2_matching(A)
             A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
         n, nnz = A.n_rows, A.nnz
-        if n <= _core.SMALL_LEVEL_ROWS:
+        if n <= _core.DILU_SMALL_ROWS:
             sys.exit("--section dilu_lanes: level too small for the "
                      "per-color path; raise --size")
         col = MatrixColoring.create(A, ConfigScope(None, {}))
@@ -148,14 +149,85 @@ def bench_dilu_lanes(A, iters, sync, rec):
                 iters, sync), entries_per_row=nnz / n)
 
 
+def bench_dilu_small(A, iters, sync, rec, max_rows=32768):
+    """Three fused DILU sweeps on the levels of at most max_rows rows of the
+    SIZE_2 Galerkin chain of A, through the one-launch apply in its earlier
+    full-slab form (`full`), the one-launch split-slab apply with 1 and with 8
+    lanes per row and routed (`small_l1`, `small_l8`, `small`), and the
+    per-color sweeps (`split`). Per form three figures, in microseconds per
+    three sweeps: `eager_us` back-to-back calls timed on the host (launch cost
+    included), `graph_us` back-to-back replays of the captured calls, and
+    `cold_us` one replay after a streaming pass over 512 MiB has evicted the
+    level from the caches, timed with events, median of the repetitions: a
+    V-cycle meets each level cold, after the fine levels' traffic."""
+    from amgx_amd import _core, ops
+    from amgx_amd.amg.coloring import MatrixColoring
+    from amgx_amd.config import ConfigScope
+    from amgx_amd.ops import gpu as G
+
+    forms = (("full", dict(form="small_full")),
+             ("small_l1", dict(form="small", lanes=1)),
+             ("small_l8", dict(form="small", lanes=8)),
+             ("small", dict(form="small")),
+             ("split", dict(form="split")))
+    evict = torch.zeros(512 << 18, dtype=torch.float32, device=A.device)
+    side = torch.cuda.Stream()
+    reps = max(iters, 5)
+    while A.n_rows >= 48:
+        n, nnz = A.n_rows, A.nnz
+        if n <= max_rows:
+            col = MatrixColoring.create(A, ConfigScope(None, {}))
+            einv = ops.dilu_setup(A, col)
+            b = torch.ones(A.n_cols, dtype=torch.float64, device=A.device)
+            x = torch.zeros_like(b)
+            nnz_u = G._slab_part(G._slabs(A, col), True)[1].numel()
+            print(f"{n} rows, {nnz / n:.2f} entries/row (U {nnz_u / n:.2f}), "
+                  f"{col.num_colors} colors, one-launch routing: "
+                  f"{n <= _core.DILU_SMALL_ROWS}", file=sys.stderr)
+            for name, how in forms:
+                def run():
+                    G.dilu_smooth(A, einv, col, b, x, 0.75, sweeps=3, **how)
+                eager = bench(run, iters, sync)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    run()
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=side):
+                        run()
+                torch.cuda.current_stream().wait_stream(side)
+                warm = bench(graph.replay, iters, sync)
+                cold = []
+                for _ in range(reps):
+                    evict.add_(1.0)
+                    t0 = torch.cuda.Event(enable_timing=True)
+                    t1 = torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    graph.replay()
+                    t1.record()
+                    sync()
+                    cold.append(t0.elapsed_time(t1) * 1e-3)
+                cold.sort()
+                del graph
+                rec(f"dilu_small_{name}_n{n}", eager, rows=n,
+                    entries_per_row=nnz / n, colors=col.num_colors,
+                    eager_us=eager * 1e6, graph_us=warm * 1e6,
+                    cold_us=cold[len(cold) // 2] * 1e6,
+                    cold_min_us=cold[0] * 1e6)
+        agg, num = ops.size2_matching(A)
+        A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=192)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--section", default="all",
-                    choices=("all", "multi_pairwise", "dilu_lanes"),
+                    choices=("all", "multi_pairwise", "dilu_lanes",
+                             "dilu_small"),
                     help="multi_pairwise: only the MULTI_PAIRWISE records; "
-                         "dilu_lanes: the DILU sweeps by lanes per row")
+                         "dilu_lanes: the DILU sweeps by lanes per row; "
+                         "dilu_small: the one-launch DILU apply against the "
+                         "per-color sweeps on the small Galerkin levels")
     args = ap.parse_args()
     sys.path.insert(0, ".")
     from amgx_amd import ops
@@ -193,6 +265,11 @@ def main():
         if dev == "cpu":
             sys.exit("--section dilu_lanes times device kernels: no GPU")
         bench_dilu_lanes(A, args.iters, sync, rec)
+        return
+    if args.section == "dilu_small":
+        if dev == "cpu":
+            sys.exit("--section dilu_small times device kernels: no GPU")
+        bench_dilu_small(A, args.iters, sync, rec)
         return
 
     rec("csrmv", bench(lambda: ops.spmv(A, x, y), args.iters, sync),

@@ -34,7 +34,7 @@ tot = {"fwd": 0, "bwd_split": 0, "bwd_full": 0, "memset": 0, "axpy": 0,
 for i, lvl in enumerate(hier.levels[:-1]):
     M = lvl.A
     n, nnz = M.n_rows, M.nnz
-    split = n > _core.SMALL_LEVEL_ROWS
+    split = n > _core.DILU_SMALL_ROWS
     rec = {"level": i, "n": n, "nnz": nnz, "colors": M.coloring.num_colors,
            "per_color_path": split}
     if split:
