@@ -564,6 +564,26 @@ int64_t dilu_lanes(double entries_per_row, bool split) {
     return entries_per_row <= t ? 1 : 8;
 }
 
+// Stream form of a per-color sweep (amgx_hip::DILU_STREAM) instead of the
+// lane form, from the slab's average entries per row and the rows of the
+// color. Measured on MI355X (profiles/NOTES.md, "DILU stream form"): on the
+// 192^3 matrix and its first two Galerkin levels the stream form is the
+// fastest on every slab (full 6.97 / 10.14 / 12.63 entries per row, L and U
+// 2.98 / 4.57 / 5.82), 14 to 30 % under the better lane form. Down the
+// Galerkin chain of a 64^3 cube it wins at 43.7 k and 13.5 k rows per color,
+// ties at 5.7 k and loses 2 to 5 % from 2.5 k down: a small color has too few
+// 64-row waves to cover the latency of their windows. The chain is measured
+// per level and a level's colors differ widely in size, so the boundary is
+// kept on the safe side: colors under 16 k rows keep their lane form,
+// whatever the slab.
+constexpr int64_t DILU_STREAM_MIN_ROWS_FULL = 1 << 14;
+constexpr int64_t DILU_STREAM_MIN_ROWS_SPLIT = 1 << 14;
+bool dilu_stream(double entries_per_row, int64_t color_rows, bool split) {
+    int64_t least = split ? DILU_STREAM_MIN_ROWS_SPLIT
+                          : DILU_STREAM_MIN_ROWS_FULL;
+    return entries_per_row > 0.0 && color_rows >= least;
+}
+
 // per-color scalar DILU apply x += relax * M^{-1} rhs over the strict
 // color-split slabs; w is the scratch vector (column-extended).
 // fused: rhs is b, the forward sweep reads the full slab (ro_f, ci_f, va_f)
@@ -577,15 +597,24 @@ int64_t dilu_lanes(double entries_per_row, bool split) {
 // counts are the tensors' sizes, no read-back; the forward slab of a plain
 // apply and U are split parts), 1 or 8 forces that form for both sweeps
 // (tests and bench_kernels.py).
+// form: 0 routes each color of each slab between its lane form and the
+// stream form (dilu_stream; a forced lanes keeps the lane forms), 1 keeps
+// the lane forms, 2 takes the stream form for every color and goes with
+// lanes = 0 only. All forms give the same bits.
 void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                 Tensor ci_u, Tensor va_u, Tensor einv_s, Tensor rows_sorted,
                 std::vector<int64_t> bounds, Tensor rhs, Tensor w, Tensor x,
                 double relax, bool fused, int64_t lanes,
-                c10::optional<Tensor> y_opt) {
+                c10::optional<Tensor> y_opt, int64_t form) {
     int64_t n = (int64_t)ro_u.numel() - 1;
     TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
                     einv_s.numel() == n,
                 "dilu_split: slabs, rows_sorted and Einv disagree on n");
+    TORCH_CHECK(form == 0 || form == 1 || form == 2,
+                "dilu_split: form must be 0 (routed), 1 (lane forms) or 2 "
+                "(stream form)");
+    TORCH_CHECK(form != 2 || lanes == 0,
+                "dilu_split: the stream form takes no lanes");
     TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n,
                 "dilu_split: color bounds do not cover the n rows");
     TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
@@ -613,6 +642,13 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                         : (int)dilu_lanes((double)ci_f.numel() / rows, !fused);
     int lanes_u = lanes ? (int)lanes
                         : (int)dilu_lanes((double)ci_u.numel() / rows, true);
+    const double epr_f = (double)ci_f.numel() / rows;
+    const double epr_u = (double)ci_u.numel() / rows;
+    auto pick = [&](int lane_form, double epr, int64_t count, bool split) {
+        bool stream = form == 2 || (form == 0 && lanes == 0 &&
+                                    dilu_stream(epr, count, split));
+        return stream ? amgx_hip::DILU_STREAM : lane_form;
+    };
     DISPATCH(AMGX_VALUE_PAIRS, "dilu_split", (va_f, x), [&] {
         hipStream_t st = cur_stream();
         if (fused)
@@ -625,20 +661,21 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                     iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                     (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(x),
-                    dptr<scalar_v>(w), dptr<scalar_v>(y), lanes_f, st);
+                    dptr<scalar_v>(w), dptr<scalar_v>(y),
+                    pick(lanes_f, epr_f, e - s, false), st);
             else
                 amgx_hip::dilu_fwd_lower<scalar_a, scalar_v>(
                     iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                     (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(w),
-                    lanes_f, st);
+                    pick(lanes_f, epr_f, e - s, true), st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_bwd_upper<scalar_a, scalar_v>(
                 iptr(ro_u) + s, iptr(ci_u), dptr<scalar_a>(va_u),
                 dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                 (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(x),
-                (scalar_v)relax, lanes_u, st);
+                (scalar_v)relax, pick(lanes_u, epr_u, e - s, true), st);
         });
     });
 }
@@ -1242,16 +1279,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               arg("fused"), arg("lanes") = 0, arg("y") = pybind11::none(),
               arg("sweeps") = 1, arg("any_size") = false);
     }
-    {   // trailing lanes / y are optional: 14 positional arguments still work
+    {   // trailing lanes / y / form are optional: 14 positional arguments
+        // still work
         using pybind11::arg;
         m.def("dilu_split", &dilu_split, arg("ro_f"), arg("ci_f"),
               arg("va_f"), arg("ro_u"), arg("ci_u"), arg("va_u"),
               arg("einv_s"), arg("rows_sorted"), arg("bounds"), arg("rhs"),
               arg("w"), arg("x"), arg("relax"), arg("fused"),
-              arg("lanes") = 0, arg("y") = pybind11::none());
+              arg("lanes") = 0, arg("y") = pybind11::none(),
+              arg("form") = 0);
     }
     m.def("dilu_lanes", &dilu_lanes, pybind11::arg("entries_per_row"),
           pybind11::arg("split") = false);
+    // the stream form of the per-color sweeps: its routing rule and geometry
+    m.def("dilu_stream", &dilu_stream, pybind11::arg("entries_per_row"),
+          pybind11::arg("color_rows"), pybind11::arg("split") = false);
+    m.def("dilu_stream_window", &amgx_hip::dilu_stream_window_of,
+          pybind11::arg("pair_bytes") = 16);
+    m.attr("DILU_STREAM_ROWS") = amgx_hip::DILU_STREAM_ROWS;
+    m.attr("DILU_STREAM_WINDOW") = amgx_hip::DILU_STREAM_WINDOW;
+    m.attr("DILU_STREAM_MIN_ROWS_FULL") = DILU_STREAM_MIN_ROWS_FULL;
+    m.attr("DILU_STREAM_MIN_ROWS_SPLIT") = DILU_STREAM_MIN_ROWS_SPLIT;
     m.def("slab_split", &slab_split);
     m.def("color_minmax", &color_minmax);
     m.def("size2_match", &size2_match);

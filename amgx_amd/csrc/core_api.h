@@ -179,6 +179,21 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
 // w_i = Einv_i (rhs_i - sum_L a_ij w_j), no pre-zeroed w; backward in place
 // z_i = w_i - Einv_i sum_U a_ij w_j stored to w[i], with x[i] += relax * z_i
 // folded in.
+// lanes = DILU_STREAM selects the stream form of the same three sweeps (same
+// bits again): a wave takes DILU_STREAM_ROWS consecutive rows of the color,
+// one lane per row, and streams their contiguous entries through a
+// wave-private LDS window of DILU_STREAM_WINDOW_BYTES bytes, which holds
+// dilu_stream_window_of(bytes of one value and one gathered vector entry)
+// entries: 512 in fp64 and with an fp32 matrix, 256 in complex128.
+constexpr int DILU_STREAM = 64;
+constexpr int DILU_STREAM_ROWS = 64;
+constexpr int DILU_STREAM_WINDOW_BYTES = 8192;
+constexpr int DILU_STREAM_WINDOW = 512;
+constexpr int dilu_stream_window_of(int pair_bytes) {
+    int w = DILU_STREAM_WINDOW_BYTES / pair_bytes;
+    w -= w % 64;
+    return w < DILU_STREAM_WINDOW ? w : DILU_STREAM_WINDOW;
+}
 template <typename TV>
 void dilu_y_init(const TV* x, TV* y, long long n, hipStream_t s);
 template <typename TA, typename TV>

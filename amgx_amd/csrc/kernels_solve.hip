@@ -562,6 +562,94 @@ __device__ __forceinline__ TV slab_row_dot_lanes(const int* __restrict__ ro_s,
     }
 }
 
+// The same product in stream form: a wave owns the 64 consecutive slab rows
+// from t0, one lane per row: lane l has row t0 + l and passes its bounds
+// rs = ro_s[t0 + l], re = ro_s[t0 + l + 1], or rs = re = 0 past the color's
+// end. Their entries are the contiguous range [ro_s[t0],
+// ro_s[min(t0 + 64, count)]), which the wave walks in windows of W entries
+// (dilu_stream_window) kept in its private LDS region `lds`: all lanes load
+// ci and va of the window coalesced, gather v through every index, and
+// write (a, g) to slot k - base; then each lane folds the part of its own
+// row that lies in the window, ascending k, with the expression of
+// slab_row_dot, and carries the sum into the next window. A row longer than a
+// window, or cut by a window's edge, takes no other path, so every row gives
+// the bits of the one-lane form. The slab loads of the next window are issued
+// once this window's registers are in LDS, so they fly during the fold.
+// Invariants: every LDS slot index is k - base with 0 <= k - base < W; a
+// load index is clamped to the last entry of the wave's range, so nothing
+// is read past the slab's end or gathered through an index that was never
+// set (the slots such lanes fill are beyond every row's end and are never
+// folded); the window loop's trip count is uniform over the wave and no lane
+// leaves it early. LDS writes and the fold are ordered within the wave alone
+// (wavefront-scope fences): the trip count differs between the waves of a
+// block, so there is no workgroup barrier in here. All 64 lanes call this
+// together.
+template <typename TA, typename TV>
+constexpr int dilu_stream_window() {
+    return dilu_stream_window_of((int)(sizeof(TA) + sizeof(TV)));
+}
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <typename TA, typename TV>
+__device__ __forceinline__ TV slab_row_dot_stream(
+    const int* __restrict__ ci_s, const TA* __restrict__ va_s, int t0,
+    int count, int lane, int rs, int re, const TV* v, char* lds) {
+    constexpr int W = dilu_stream_window<TA, TV>();
+    constexpr int U = W / 64;
+    TA* la = reinterpret_cast<TA*>(lds);
+    TV* lg = reinterpret_cast<TV*>(lds + W * sizeof(TA));
+    // the wave's range, from its first and its last row (lane 0 has a row)
+    const int last = (count - t0 < DILU_STREAM_ROWS ? count - t0
+                                                    : DILU_STREAM_ROWS) - 1;
+    const int kb = __builtin_amdgcn_readfirstlane(rs);
+    const int ke = __builtin_amdgcn_readlane(
+        re, __builtin_amdgcn_readfirstlane(last));
+    TV sum = TV(0);
+    int c[U];
+    TA a[U];
+    auto load_window = [&](int base) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int k = base + u * 64 + lane;
+            k = k < ke ? k : ke - 1;
+            a[u] = va_s[k];
+            c[u] = ci_s[k];
+        }
+    };
+    if (kb < ke) load_window(kb);
+    for (int base = kb; base < ke; base += W) {
+        TV g[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) g[u] = v[c[u]];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            la[u * 64 + lane] = a[u];
+            lg[u * 64 + lane] = g[u];
+        }
+        // the next window's slab loads fly during this window's fold
+        if (base + W < ke) load_window(base + W);
+        wave_lds_sync();
+        int k = (rs > base ? rs : base) - base;
+        const int e = (re < base + W ? re : base + W) - base;
+        for (; k + 4 <= e; k += 4) {
+            TA a0 = la[k], a1 = la[k + 1], a2 = la[k + 2], a3 = la[k + 3];
+            TV g0 = lg[k], g1 = lg[k + 1], g2 = lg[k + 2], g3 = lg[k + 3];
+            sum += (TV)a0 * g0;
+            sum += (TV)a1 * g1;
+            sum += (TV)a2 * g2;
+            sum += (TV)a3 * g3;
+        }
+        for (; k < e; ++k) sum += (TV)la[k] * lg[k];
+        wave_lds_sync();
+    }
+    return sum;
+}
+
 // ============================================================ multicolor GS
 // color-sorted GS row sweep (reorder-by-color layout; ro_s/rows/dinv_s
 // pre-offset to the color base, matrix arrays gathered in rows_sorted
@@ -914,6 +1002,112 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_upper(
     x[i] += relax * z;
 }
 
+// The products of a row's epilogue in the stream kernels. In a complex product
+// a * o the compiler contracts the imaginary part a.re * o.im + a.im * o.re
+// to one rounded product and one fused multiply-add, and which of the two
+// products it rounds depends on the code around the expression: in the lane
+// forms Einv_i (b_i - sum) and relax * z round a.re * o.im, Einv_i * sum of
+// the backward kernel rounds a.im * o.re (read off their ISA;
+// tests/test_gpu_dilu_stream.py compares the bits). The stream kernels spell
+// the choice out, so they give the lane forms' bits whatever surrounds the
+// call. A real product is a real product.
+__device__ __forceinline__ double fma_of(double a, double b, double c) {
+    return __builtin_fma(a, b, c);
+}
+__device__ __forceinline__ float fma_of(float a, float b, float c) {
+    return __builtin_fmaf(a, b, c);
+}
+template <bool ROUND_RE_IM, typename T>
+__device__ __forceinline__ T times_pinned(T e, T s) {
+    return e * s;
+}
+template <bool ROUND_RE_IM, typename R>
+__device__ __forceinline__ cplx<R> times_pinned(const cplx<R>& e,
+                                              const cplx<R>& s) {
+#pragma clang fp contract(off)
+    R re = fma_of(e.re, s.re, -(e.im * s.im));
+    R im = ROUND_RE_IM ? fma_of(e.im, s.re, e.re * s.im)
+                       : fma_of(e.re, s.im, e.im * s.re);
+    return cplx<R>(re, im);
+}
+
+// Stream forms of the three kernels above (slab_row_dot_stream): a block of
+// DILU_STREAM_WAVES waves, 64 rows of the color per wave, one LDS region per
+// wave. The row's own reads are issued ahead of the windows, so they overlap
+// the slab loads; the stores are those of the lane forms. A wave past the
+// color's end leaves as a whole, before any window; in the color's last wave
+// a lane without a row reads as the color's last row (tc) and stores nothing.
+constexpr int DILU_STREAM_WAVES = AMGX_BLOCK / 64;
+static inline int dilu_stream_grid(int count) {
+    const int per_block = DILU_STREAM_WAVES * DILU_STREAM_ROWS;
+    return (count + per_block - 1) / per_block;
+}
+#define DILU_STREAM_PROLOGUE(RO)                                               \
+    __shared__ __attribute__((aligned(16))) char                               \
+        lds[DILU_STREAM_WAVES * DILU_STREAM_WINDOW_BYTES];                     \
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;                \
+    const long long t0l =                                                      \
+        ((long long)blockIdx.x * DILU_STREAM_WAVES + wave) * DILU_STREAM_ROWS; \
+    if (t0l >= count) return;                                                  \
+    const int t0 = (int)t0l;                                                   \
+    const bool has_row = t0 + lane < count;                                    \
+    const int tc = has_row ? t0 + lane : count - 1;                            \
+    int rs = RO[tc], re = RO[tc + 1];                                          \
+    const int i = rows[tc];                                                    \
+    const TA ei = einv_s[tc];                                                  \
+    if (!has_row) rs = re = 0;                                                 \
+    char* region = lds + wave * DILU_STREAM_WINDOW_BYTES
+
+template <typename TA, typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_stream_full(
+    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
+    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
+    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
+    const TV* __restrict__ x, TV* __restrict__ w, TV* y) {
+    DILU_STREAM_PROLOGUE(ro_s);
+    const TV ri = rhs[i], xi = x[i];
+    TV sum = slab_row_dot_stream(ci_s, va_s, t0, count, lane, rs, re, y,
+                                 region);
+    if (!has_row) return;
+    TV wi = times_pinned<true>((TV)ei, ri - sum);
+    w[i] = wi;
+    y[i] = add_unfused(xi, wi);
+}
+
+template <typename TA, typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_stream_lower(
+    const int* __restrict__ ro_l, const int* __restrict__ ci_l,
+    const TA* __restrict__ va_l, const TA* __restrict__ einv_s,
+    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
+    TV* w) {
+    DILU_STREAM_PROLOGUE(ro_l);
+    const TV ri = rhs[i];
+    TV sum = slab_row_dot_stream(ci_l, va_l, t0, count, lane, rs, re, w,
+                                 region);
+    if (!has_row) return;
+    w[i] = times_pinned<true>((TV)ei, ri - sum);
+}
+
+// w[i] is this color's own, still the forward w: read ahead of the windows
+template <typename TA, typename TV>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_stream_upper(
+    const int* __restrict__ ro_u, const int* __restrict__ ci_u,
+    const TA* __restrict__ va_u, const TA* __restrict__ einv_s,
+    const int* __restrict__ rows, int count, TV* w, TV* __restrict__ x,
+    TV relax) {
+    DILU_STREAM_PROLOGUE(ro_u);
+    const TV wi = w[i];
+    TV xi = x[i];
+    TV sum = slab_row_dot_stream(ci_u, va_u, t0, count, lane, rs, re, w,
+                                 region);
+    if (!has_row) return;
+    TV z = wi - times_pinned<false>((TV)ei, sum);
+    w[i] = z;
+    xi += times_pinned<true>(relax, z);
+    x[i] = xi;
+}
+#undef DILU_STREAM_PROLOGUE
+
 // block forward: w_i = Einv_i (rhs_i - sum_{color(j)<c} A_ij w_j); w
 // pre-zeroed so the full-row product only picks up earlier colors.
 // block backward: z_i = w_i - Einv_i sum_{color(j)>c} A_ij z_j; z pre-zeroed
@@ -1170,10 +1364,15 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
     }
 }
 
-// LANES of a scalar per-color launch: 1 or 8 lanes per row
-#define DILU_LANES_LAUNCH(kernel, lanes, count, s, ...)                        \
+// LANES of a scalar per-color launch: 1 or 8 lanes per row, or DILU_STREAM
+// for the stream form `skernel`
+#define DILU_LANES_LAUNCH(kernel, skernel, lanes, count, s, ...)               \
     do {                                                                       \
-        if ((lanes) == 8)                                                      \
+        if ((lanes) == DILU_STREAM)                                            \
+            hipLaunchKernelGGL((skernel<TA, TV>),                              \
+                               dim3(dilu_stream_grid(count)),                  \
+                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
+        else if ((lanes) == 8)                                                 \
             hipLaunchKernelGGL((kernel<8, TA, TV>),                            \
                                dim3(grid_1d((long long)(count) * 8)),          \
                                dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
@@ -1181,7 +1380,8 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
             hipLaunchKernelGGL((kernel<1, TA, TV>), dim3(grid_1d(count)),      \
                                dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
         else                                                                   \
-            throw std::runtime_error(#kernel ": lanes must be 1 or 8");        \
+            throw std::runtime_error(                                          \
+                #kernel ": lanes must be 1, 8 or DILU_STREAM");                \
     } while (0)
 
 template <typename TV>
@@ -1197,8 +1397,9 @@ void dilu_fwd_full(const int* ro_s, const int* ci_s, const TA* va_s,
                    const TV* rhs, const TV* x, TV* w, TV* y, int lanes,
                    hipStream_t s) {
     if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_fwd_scalar_full, lanes, count, s, ro_s, ci_s, va_s,
-                      einv_s, rows, count, rhs, x, w, y);
+    DILU_LANES_LAUNCH(dilu_fwd_scalar_full, dilu_fwd_stream_full, lanes,
+                      count, s, ro_s, ci_s, va_s, einv_s, rows, count, rhs, x,
+                      w, y);
 }
 
 template <typename TA, typename TV>
@@ -1206,8 +1407,9 @@ void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
                     const TA* einv_s, const int* rows, int count,
                     const TV* rhs, TV* w, int lanes, hipStream_t s) {
     if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_fwd_scalar_lower, lanes, count, s, ro_l, ci_l,
-                      va_l, einv_s, rows, count, rhs, w);
+    DILU_LANES_LAUNCH(dilu_fwd_scalar_lower, dilu_fwd_stream_lower, lanes,
+                      count, s, ro_l, ci_l, va_l, einv_s, rows, count, rhs,
+                      w);
 }
 
 template <typename TA, typename TV>
@@ -1215,8 +1417,9 @@ void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
                     const TA* einv_s, const int* rows, int count, TV* w,
                     TV* x, TV relax, int lanes, hipStream_t s) {
     if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_bwd_scalar_upper, lanes, count, s, ro_u, ci_u,
-                      va_u, einv_s, rows, count, w, x, relax);
+    DILU_LANES_LAUNCH(dilu_bwd_scalar_upper, dilu_bwd_stream_upper, lanes,
+                      count, s, ro_u, ci_u, va_u, einv_s, rows, count, w, x,
+                      relax);
 }
 #undef DILU_LANES_LAUNCH
 

@@ -352,7 +352,7 @@ def _gather_part(va_s, part):
     return out
 
 
-DILU_FORMS = ("split", "small", "small_full")
+DILU_FORMS = ("split", "small", "small_full", "stream")
 
 
 def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
@@ -361,7 +361,8 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
     ("small") up to DILU_SMALL_ROWS rows and the per-color sweeps ("split")
     past it; form (tests, bench_kernels.py) names one of DILU_FORMS whatever
     the size, "small_full" being the one-launch apply in its earlier
-    full-slab form."""
+    full-slab form and "stream" the per-color sweeps in their stream form for
+    every color (it goes with lanes=0 only)."""
     n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
     w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
     st = _slabs(A, coloring)
@@ -375,7 +376,7 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
         form = "split" if _split_path(A) else "small"
     elif form not in DILU_FORMS:
         raise ValueError(f"form must be one of {DILU_FORMS}")
-    if form in ("split", "small"):
+    if form in ("split", "small", "stream"):
         ro_u, ci_u, _ = _slab_part(st, True)
         y = None
         if fused:
@@ -397,7 +398,8 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
             _core.dilu_split(*fwd, ro_u, ci_u, Einv.va_u, Einv.einv_s,
                              coloring.rows_sorted, coloring.bounds,
                              rhs.reshape(-1), w, x.reshape(-1),
-                             float(relaxation), fused, int(lanes), y)
+                             float(relaxation), fused, int(lanes), y,
+                             2 if form == "stream" else 0)
         return
     if lanes:
         raise ValueError("lanes selects the form of the split-slab sweeps; "

@@ -10,6 +10,7 @@ human table to stderr.
     python bench_kernels.py [--size 192] [--iters 20] [--section multi_pairwise]
     python bench_kernels.py [--size 192] [--iters 20] [--section dilu_lanes]
     python bench_kernels.py --size 64 --iters 50 --section dilu_small
+    python bench_kernels.py [--size 192] [--iters 20] [--section dilu_stream]
 """
 
 import argparse
@@ -93,7 +94,8 @@ def bench_dilu_lanes(A, iters, sync, rec):
     aggregation (about 7, 10 and 12.7 entries per row). A sweep is timed
     through one apply whose other sweep runs over an empty slab; `base` is
     the apply with both slabs empty (launches and row traffic only), to be
-    subtracted. The whole fused and plain applies follow."""
+    subtracted (dilu_sweep_cases). The whole fused and plain applies
+    follow."""
     from amgx_amd import _core, ops
     from amgx_amd.amg.coloring import MatrixColoring
     from amgx_amd.config import ConfigScope
@@ -109,29 +111,13 @@ def bench_dilu_lanes(A, iters, sync, rec):
                      "per-color path; raise --size")
         col = MatrixColoring.create(A, ConfigScope(None, {}))
         einv = ops.dilu_setup(A, col)
-        st = G._slabs(A, col)
-        ro_u, ci_u, _ = G._slab_part(st, True)
-        ro_l, ci_l, _ = part_l = G._slab_part(st, False)
-        va_l = G._gather_part(einv.va_s, part_l)
-        ro_0 = torch.zeros_like(ro_u)
-        ci_0, va_0 = ci_u[:0], einv.va_u[:0]
         b = torch.ones(A.n_cols, dtype=torch.float64, device=A.device)
         x = torch.zeros_like(b)
         w, y = torch.empty_like(b), torch.empty_like(b)
-        full = (st.ro_s, st.ci_s, einv.va_s)
-        lower, upper = (ro_l, ci_l, va_l), (ro_u, ci_u, einv.va_u)
-        empty = (ro_0, ci_0, va_0)
-        # bytes: offsets + rows_sorted + Einv per sweep, then the row's own
-        # reads and writes (bench_kernels.py main, dilu records)
-        sweep = n * 16 + 4
-        cases = (("base", empty, empty, False, None),
-                 ("fwd_full", full, empty, True, nnz * 12 + sweep + n * 40),
-                 ("fwd_lower", lower, empty, False,
-                  ci_l.numel() * 12 + sweep + n * 24),
-                 ("bwd_upper", empty, upper, False,
-                  ci_u.numel() * 12 + sweep + n * 32))
+        cases = dilu_sweep_cases(A, col, einv)
         print(f"level {level}: {n} rows, {nnz / n:.2f} entries/row "
-              f"(L {ci_l.numel() / n:.2f}, U {ci_u.numel() / n:.2f}), "
+              f"(L {cases[2][1][1].numel() / n:.2f}, "
+              f"U {cases[3][2][1].numel() / n:.2f}), "
               f"{col.num_colors} colors", file=sys.stderr)
         for name, fwd, bwd, fused, nbytes in cases:
             for lanes in (1, 8):
@@ -147,6 +133,127 @@ def bench_dilu_lanes(A, iters, sync, rec):
             rec(f"dilu_apply_g{level}_l{lanes}", bench(
                 lambda: G.dilu_solve(A, einv, col, b, 0.75, x, lanes=lanes),
                 iters, sync), entries_per_row=nnz / n)
+
+
+def eager_graph_cold(run, iters, sync, evict, side):
+    """Seconds per eager call of run, and the record fields eager_us,
+    graph_us, cold_us and cold_min_us described at bench_dilu_small; evict is
+    the 512 MiB buffer streamed before each cold replay, side the capture
+    stream."""
+    eager = bench(run, iters, sync)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            run()
+    torch.cuda.current_stream().wait_stream(side)
+    warm = bench(graph.replay, iters, sync)
+    cold = []
+    for _ in range(max(iters, 5)):
+        evict.add_(1.0)
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        graph.replay()
+        t1.record()
+        sync()
+        cold.append(t0.elapsed_time(t1) * 1e-3)
+    cold.sort()
+    del graph
+    return eager, dict(eager_us=eager * 1e6, graph_us=warm * 1e6,
+                       cold_us=cold[len(cold) // 2] * 1e6,
+                       cold_min_us=cold[0] * 1e6)
+
+
+def dilu_sweep_cases(A, col, einv):
+    """(name, forward slab, backward slab, fused, bytes) of the apply with
+    both slabs empty (`base`: launches and row traffic only, to be
+    subtracted) and of each sweep alone, its other sweep over an empty slab.
+    Bytes: offsets + rows_sorted + Einv per sweep, then the row's own reads
+    and writes (bench_kernels.py main, dilu records)."""
+    from amgx_amd.ops import gpu as G
+
+    n, nnz = A.n_rows, A.nnz
+    st = G._slabs(A, col)
+    ro_u, ci_u, _ = G._slab_part(st, True)
+    ro_l, ci_l, _ = part_l = G._slab_part(st, False)
+    va_l = G._gather_part(einv.va_s, part_l)
+    empty = (torch.zeros_like(ro_u), ci_u[:0], einv.va_u[:0])
+    full = (st.ro_s, st.ci_s, einv.va_s)
+    lower, upper = (ro_l, ci_l, va_l), (ro_u, ci_u, einv.va_u)
+    sweep = n * 16 + 4
+    return (("base", empty, empty, False, None),
+            ("fwd_full", full, empty, True, nnz * 12 + sweep + n * 40),
+            ("fwd_lower", lower, empty, False,
+             ci_l.numel() * 12 + sweep + n * 24),
+            ("bwd_upper", empty, upper, False,
+             ci_u.numel() * 12 + sweep + n * 32))
+
+
+def bench_dilu_stream(A, iters, sync, rec, min_rows=1400):
+    """The three scalar per-color DILU sweeps in their stream form next to 1
+    and 8 lanes per row, on the matrix and its first two SIZE_2 Galerkin
+    levels, timed as in bench_dilu_lanes (`base` to be subtracted; the stream
+    form of an empty slab is the lane launch, so `base` has no stream record).
+    Then three fused sweeps per form, and routed, on the SIZE_2 chain of a 64^3
+    cube down to min_rows rows, where the colors are small: eager, graph
+    replay and cold as in bench_dilu_small."""
+    from amgx_amd import _core, ops
+    from amgx_amd.amg.coloring import MatrixColoring
+    from amgx_amd.config import ConfigScope
+    from amgx_amd.ops import gpu as G
+    from amgx_amd.problems import poisson_3d
+
+    forms = (("l1", 1, 1), ("l8", 8, 1), ("stream", 0, 2))
+    for level in range(3):
+        if level:
+            agg, num = ops.size2_matching(A)
+            A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
+        n, nnz = A.n_rows, A.nnz
+        col = MatrixColoring.create(A, ConfigScope(None, {}))
+        einv = ops.dilu_setup(A, col)
+        b = torch.ones(A.n_cols, dtype=torch.float64, device=A.device)
+        x = torch.zeros_like(b)
+        w, y = torch.empty_like(b), torch.empty_like(b)
+        sizes = [e - s for s, e in zip(col.bounds[:-1], col.bounds[1:])]
+        print(f"level {level}: {n} rows, {nnz / n:.2f} entries/row, "
+              f"{col.num_colors} colors of {min(sizes)}..{max(sizes)} rows",
+              file=sys.stderr)
+        for name, fwd, bwd, fused, nbytes in dilu_sweep_cases(A, col, einv):
+            for tag, lanes, form in forms:
+                if name == "base" and form == 2:
+                    continue
+                sec = bench(lambda: _core.dilu_split(
+                    *fwd, *bwd, einv.einv_s, col.rows_sorted, col.bounds, b,
+                    w, x, 0.75, fused, lanes, y, form), iters, sync)
+                rec(f"dilu_stream_{name}_g{level}_{tag}", sec, nbytes,
+                    rows=n, colors=col.num_colors,
+                    entries_per_row=(fwd[1].numel() + bwd[1].numel()) / n)
+    chain = (("l1", dict(form="split", lanes=1)),
+             ("l8", dict(form="split", lanes=8)),
+             ("stream", dict(form="stream")),
+             ("routed", dict(form="split")))
+    A = poisson_3d(64, 64, 64, device=A.device)
+    evict = torch.zeros(512 << 18, dtype=torch.float32, device=A.device)
+    side = torch.cuda.Stream()
+    while A.n_rows >= min_rows:
+        n, nnz = A.n_rows, A.nnz
+        col = MatrixColoring.create(A, ConfigScope(None, {}))
+        einv = ops.dilu_setup(A, col)
+        b = torch.ones(A.n_cols, dtype=torch.float64, device=A.device)
+        x = torch.zeros_like(b)
+        for name, how in chain:
+            def run():
+                G.dilu_smooth(A, einv, col, b, x, 0.75, sweeps=3, **how)
+            eager, times = eager_graph_cold(run, iters, sync, evict, side)
+            # three sweeps: y pass, full slab forward, U backward
+            rec(f"dilu_stream_chain_{name}_n{n}", eager,
+                3 * (nnz * 18 + n * 120), rows=n, entries_per_row=nnz / n,
+                colors=col.num_colors, rows_per_color=n / col.num_colors,
+                **times)
+        agg, num = ops.size2_matching(A)
+        A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
 
 
 def bench_dilu_small(A, iters, sync, rec, max_rows=32768):
@@ -172,7 +279,6 @@ def bench_dilu_small(A, iters, sync, rec, max_rows=32768):
              ("split", dict(form="split")))
     evict = torch.zeros(512 << 18, dtype=torch.float32, device=A.device)
     side = torch.cuda.Stream()
-    reps = max(iters, 5)
     while A.n_rows >= 48:
         n, nnz = A.n_rows, A.nnz
         if n <= max_rows:
@@ -187,32 +293,9 @@ def bench_dilu_small(A, iters, sync, rec, max_rows=32768):
             for name, how in forms:
                 def run():
                     G.dilu_smooth(A, einv, col, b, x, 0.75, sweeps=3, **how)
-                eager = bench(run, iters, sync)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    run()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side):
-                        run()
-                torch.cuda.current_stream().wait_stream(side)
-                warm = bench(graph.replay, iters, sync)
-                cold = []
-                for _ in range(reps):
-                    evict.add_(1.0)
-                    t0 = torch.cuda.Event(enable_timing=True)
-                    t1 = torch.cuda.Event(enable_timing=True)
-                    t0.record()
-                    graph.replay()
-                    t1.record()
-                    sync()
-                    cold.append(t0.elapsed_time(t1) * 1e-3)
-                cold.sort()
-                del graph
+                eager, times = eager_graph_cold(run, iters, sync, evict, side)
                 rec(f"dilu_small_{name}_n{n}", eager, rows=n,
-                    entries_per_row=nnz / n, colors=col.num_colors,
-                    eager_us=eager * 1e6, graph_us=warm * 1e6,
-                    cold_us=cold[len(cold) // 2] * 1e6,
-                    cold_min_us=cold[0] * 1e6)
+                    entries_per_row=nnz / n, colors=col.num_colors, **times)
         agg, num = ops.size2_matching(A)
         A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
 
@@ -223,11 +306,13 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--section", default="all",
                     choices=("all", "multi_pairwise", "dilu_lanes",
-                             "dilu_small"),
+                             "dilu_small", "dilu_stream"),
                     help="multi_pairwise: only the MULTI_PAIRWISE records; "
                          "dilu_lanes: the DILU sweeps by lanes per row; "
                          "dilu_small: the one-launch DILU apply against the "
-                         "per-color sweeps on the small Galerkin levels")
+                         "per-color sweeps on the small Galerkin levels; "
+                         "dilu_stream: the stream form of the DILU sweeps "
+                         "against the lane forms")
     args = ap.parse_args()
     sys.path.insert(0, ".")
     from amgx_amd import ops
@@ -265,6 +350,11 @@ def main():
         if dev == "cpu":
             sys.exit("--section dilu_lanes times device kernels: no GPU")
         bench_dilu_lanes(A, args.iters, sync, rec)
+        return
+    if args.section == "dilu_stream":
+        if dev == "cpu":
+            sys.exit("--section dilu_stream times device kernels: no GPU")
+        bench_dilu_stream(A, args.iters, sync, rec)
         return
     if args.section == "dilu_small":
         if dev == "cpu":
