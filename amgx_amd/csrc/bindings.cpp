@@ -105,6 +105,15 @@ inline void check_scalar_if_complex(const Tensor& va, int64_t b,
                 ": complex block matrices are unsupported");
 }
 
+// the block smoother kernels keep a block or a vector of block_dim components
+// in private arrays of MAX_BLOCK_DIM (core_api.h); only the block SpMV takes
+// any block size
+inline void check_block_dim(int64_t b, const char* name) {
+    TORCH_CHECK(b >= 1 && b <= amgx_hip::MAX_BLOCK_DIM, name, ": block_dim ",
+                b, " is outside the supported range 1..",
+                amgx_hip::MAX_BLOCK_DIM);
+}
+
 // f(c, s, e) for every non-empty color c = slots [s, e) of rows_sorted, in
 // ascending or descending color order
 template <typename F>
@@ -359,6 +368,7 @@ Tensor trans_index(Tensor ro, Tensor ci, int64_t n) {
 // ---------------------------------------------------------------- smoothers
 Tensor jacobi_dinv(Tensor ro, Tensor ci, Tensor va, Tensor didx, int64_t n,
                    int64_t b, bool l1) {
+    check_block_dim(b, "jacobi_dinv");
     auto out = b == 1 ? torch::empty({n}, va.options())
                       : torch::empty({n, b, b}, va.options());
     TORCH_CHECK(!va.is_complex() || (b == 1 && !l1),
@@ -387,6 +397,7 @@ void jacobi_smooth(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
 
 void gs_smooth_rows(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
                     Tensor bvec, Tensor x, Tensor rows, double omega) {
+    check_block_dim(b, "gs_smooth_rows");
     int n = (int)(ro.numel() - 1);
     check_scalar_if_complex(va, b, "gs_smooth_rows");
     DISPATCH(AMGX_VALUE_PAIRS, "gs_smooth_rows", (va, x), [&] {
@@ -401,6 +412,7 @@ void gs_smooth_rows(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
 void gs_sweep(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor dinv,
               Tensor bvec, Tensor x, Tensor rows_sorted,
               std::vector<int64_t> bounds, double omega, bool symmetric) {
+    check_block_dim(b, "gs_sweep");
     int n = (int)(ro.numel() - 1);
     check_scalar_if_complex(va, b, "gs_sweep");
     DISPATCH(AMGX_VALUE_PAIRS, "gs_sweep", (va, x), [&] {
@@ -449,6 +461,7 @@ void gs_sweep_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, Tensor dinv_s,
 Tensor dilu_setup(Tensor ro, Tensor ci, Tensor va, int64_t b, Tensor didx,
                   Tensor tidx, Tensor colors, Tensor rows_sorted,
                   std::vector<int64_t> bounds) {
+    check_block_dim(b, "dilu_setup");
     int n = (int)(ro.numel() - 1);
     check_scalar_if_complex(va, b, "dilu_setup");
     auto einv = b == 1 ? torch::zeros({n}, va.options())
@@ -501,6 +514,7 @@ void dilu_sorted(Tensor ro_s, Tensor ci_s, Tensor va_s, int64_t b,
                  std::vector<int64_t> bounds, Tensor bounds_dev, Tensor rhs,
                  Tensor w, Tensor z, Tensor x, double relax, bool fused,
                  bool any_size) {
+    check_block_dim(b, "dilu_sorted");
     TORCH_CHECK(!fused || b == 1 || b == 4,
                 "dilu_sorted: no fused-residual kernel for block_dim ", b);
     check_scalar_if_complex(va_s, b, "dilu_sorted");
@@ -1157,6 +1171,7 @@ std::vector<Tensor> ilu0_setup_block(Tensor ro, Tensor ci, Tensor va,
                                      int64_t b, Tensor didx, Tensor pos,
                                      Tensor rows_sorted,
                                      std::vector<int64_t> bounds) {
+    check_block_dim(b, "ilu0_setup_block");
     int n = (int)(ro.numel() - 1);
     auto lu = va.clone().reshape({-1});
     auto dinv = torch::zeros({(int64_t)n * b * b}, va.options());
@@ -1179,6 +1194,7 @@ void ilu0_apply_block(Tensor ro, Tensor ci, Tensor lu, Tensor dinv,
                       int64_t b, Tensor pos, Tensor rows_sorted,
                       std::vector<int64_t> bounds, Tensor r, Tensor y,
                       Tensor z, Tensor x, double relax) {
+    check_block_dim(b, "ilu0_apply_block");
     int n = (int)(ro.numel() - 1);
     y.zero_();
     z.zero_();

@@ -85,10 +85,19 @@ __device__ __forceinline__ T block_reduce_max(T v) {
     return v;
 }
 
-// Small fixed-size dense helpers for block-CSR work (b x b, b <= 8), row-major.
+// Small dense helpers for block-CSR work: b x b row-major, b <= 16
+// (MAX_BLOCK_DIM, core_api.h). The callers hold such a block, or one vector
+// of b components, in private arrays (BMAX = 8 or 16, acc[16]), so the
+// bindings reject larger block sizes; only the block SpMV takes any b.
+
+// Gauss-Jordan inverse with partial pivoting; m is destroyed. SINGULAR-BLOCK
+// RULE (block Jacobi and the DILU fallback target, here and in
+// ops/cpu.py:_gauss_jordan_inv): a pivot column that is exactly zero at its
+// step gets a unit pivot and the elimination goes on. Returns the smallest
+// pivot magnitude met, 0 for such a patched pivot; a NaN pivot sticks.
 template <typename T>
-__device__ __forceinline__ void small_mat_inv(T* m, T* inv, int b) {
-    // Gauss-Jordan with partial pivoting on a b x b row-major matrix.
+__device__ __forceinline__ double small_mat_inv(T* m, T* inv, int b) {
+    double pmin = HUGE_VAL;
     for (int i = 0; i < b; ++i)
         for (int j = 0; j < b; ++j) inv[i * b + j] = (i == j) ? T(1) : T(0);
     for (int k = 0; k < b; ++k) {
@@ -98,7 +107,8 @@ __device__ __forceinline__ void small_mat_inv(T* m, T* inv, int b) {
             T a = fabs((double)m[r * b + k]);
             if (a > mx) { mx = a; piv = r; }
         }
-        if (mx == T(0)) {  // singular: identity row
+        if (pmin == pmin && !((double)mx >= pmin)) pmin = (double)mx;
+        if (mx == T(0)) {  // singular: unit pivot
             m[k * b + k] = T(1);
             piv = k;
         }
@@ -121,4 +131,27 @@ __device__ __forceinline__ void small_mat_inv(T* m, T* inv, int b) {
             }
         }
     }
+    return pmin;
+}
+
+// BLOCK DILU FALLBACK RULE (dilu_setup_block, dilu_setup_b4_kernel and
+// ops/cpu.py:_dilu_block_inverse): the inverse of the modified block E_i, by
+// small_mat_inv, is kept only if
+//     max|E_i| <= 1e10 (dmax + 1)   and
+//     min_k |pivot_k| >= dilu_pivot_floor<T>() * (dmax > 0 ? dmax : 1),
+// dmax the largest magnitude in the stored diagonal block D_i (0 where the
+// row has none), both written so that a NaN fails them. That rejects a
+// non-finite E_i, one grown wildly through a bad earlier pivot, and one
+// singular to working precision. Otherwise Einv_i is the inverse of D_i, or
+// the identity where no diagonal block is stored. emax = max|E_i| taken with
+// fmax (NaN entries ignored), pmin from small_mat_inv on E_i.
+template <typename T>
+__device__ __forceinline__ double dilu_pivot_floor() {
+    return sizeof(T) == 4 ? 1e-5 : 1e-10;
+}
+template <typename T>
+__device__ __forceinline__ bool dilu_keep_inverse(double emax, double pmin,
+                                                  double dmax) {
+    return emax <= 1e10 * (dmax + 1.0) &&
+           pmin >= dilu_pivot_floor<T>() * (dmax > 0.0 ? dmax : 1.0);
 }

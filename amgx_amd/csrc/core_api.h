@@ -31,6 +31,12 @@
 
 namespace amgx_hip {
 
+// Largest block size of the block smoother kernels (Jacobi, GS, DILU,
+// ILU(0)): they keep a block, or one vector of block_dim components, in
+// private arrays of this size, and the bindings reject anything larger
+// before a launch. The block SpMV alone takes any block size.
+constexpr int MAX_BLOCK_DIM = 16;
+
 // ============================================================ kernels_solve.hip
 // Launchers marked [value] are instantiated over the value types or value
 // pairs (real and complex); all others over the real lists only. A [value]

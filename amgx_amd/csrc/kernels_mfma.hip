@@ -188,13 +188,16 @@ __global__ __launch_bounds__(256) void dilu_setup_b4_kernel(
     e_acc += __shfl_xor(e_acc, 8, 64);
     // E = D - sum; element here is (m=o, n=q) -> row-major o*4 + q
     if (g == 0) {
+        // a row without a stored diagonal block has D_i = 0, as in
+        // dilu_setup_block and on the host
         double d = (valid && dk >= 0)
                        ? (double)va[(long long)dk * 16 + o * 4 + q]
-                       : (valid && o == q ? 1.0 : 0.0);
+                       : 0.0;
         Es[wave][o * 4 + q] = d - e_acc;
     }
     __syncthreads();
-    // stabilized fallback + inversion: lane 0 of each wave (setup-time)
+    // inversion and stabilized fallback (rule at dilu_keep_inverse,
+    // common.h): lane 0 of each wave (setup-time)
     if (valid && lane == 0) {
         double emax = 0.0, dmax = 0.0;
         for (int s = 0; s < 16; ++s) {
@@ -203,12 +206,13 @@ __global__ __launch_bounds__(256) void dilu_setup_b4_kernel(
                                 : 0.0;
             dmax = fmax(dmax, dv);
         }
-        if (!(emax <= 1e10 * (dmax + 1.0))) {
+        double pmin = small_mat_inv(Es[wave], Is[wave], 4);
+        if (!dilu_keep_inverse<TA>(emax, pmin, dmax)) {
             for (int s = 0; s < 16; ++s)
                 Es[wave][s] = dk >= 0 ? (double)va[(long long)dk * 16 + s]
                                       : (s % 5 == 0 ? 1.0 : 0.0);
+            small_mat_inv(Es[wave], Is[wave], 4);
         }
-        small_mat_inv(Es[wave], Is[wave], 4);
     }
     __syncthreads();
     if (valid && lane < 16)

@@ -396,6 +396,10 @@ __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_scalar(const int* __re
     dinv[i] = T(1) / d;
 }
 
+// block: a missing diagonal block counts as zero; l1 adds the l1 norm of the
+// off-diagonal part of component r's row with the sign of D_rr (the l1 sign
+// rule of ops/cpu.py:jacobi_dinv, as in the scalar kernel above); singular
+// blocks by the rule of small_mat_inv (common.h).
 template <typename T, int BMAX>
 __global__ __launch_bounds__(AMGX_BLOCK) void jacobi_dinv_block(const int* __restrict__ ro,
                                   const T* __restrict__ va,
@@ -853,8 +857,8 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_setup_block(const int* __rest
                 }
         }
     }
-    // stabilized fallback: wildly grown E means an earlier near-singular
-    // pivot — revert to the plain diagonal block
+    // stabilized fallback to the plain diagonal block: the rule is stated at
+    // dilu_keep_inverse (common.h)
     double emax = 0.0, dmax = 0.0;
     for (int q = 0; q < b * b; ++q) {
         emax = fmax(emax, fabs((double)E[q]));
@@ -862,12 +866,13 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_setup_block(const int* __rest
                             : 0.0;
         dmax = fmax(dmax, dv);
     }
-    if (!(emax <= 1e10 * (dmax + 1.0))) {
+    double pmin = small_mat_inv(E, Inv, b);
+    if (!dilu_keep_inverse<T>(emax, pmin, dmax)) {
         for (int q = 0; q < b * b; ++q)
             E[q] = dk >= 0 ? va[(long long)dk * b * b + q]
                            : (q % (b + 1) == 0 ? T(1) : T(0));
+        small_mat_inv(E, Inv, b);
     }
-    small_mat_inv(E, Inv, b);
     for (int q = 0; q < b * b; ++q) einv[(long long)i * b * b + q] = Inv[q];
 }
 

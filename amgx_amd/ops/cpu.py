@@ -137,11 +137,54 @@ def scal(x, alpha):
     return x
 
 
+# ---------------------------------------------------------------------- blocks
+def _gauss_jordan_inv(M):
+    """Inverses of the b x b blocks M (n, b, b) and, per block, the smallest
+    pivot magnitude met: the Gauss-Jordan pass of csrc/common.h:small_mat_inv
+    step for step. The pivot of column k is the first entry of largest
+    magnitude at or below the diagonal. SINGULAR-BLOCK RULE (block Jacobi,
+    the DILU fallback target, both backends): a pivot column that is exactly
+    zero at its step gets a unit pivot and the elimination goes on; the pivot
+    magnitude recorded for it is 0. A NaN pivot magnitude sticks."""
+    m = np.array(M, dtype=np.float64, copy=True)
+    n, b, _ = m.shape
+    inv = np.broadcast_to(np.eye(b), m.shape).copy()
+    pmin = np.full(n, np.inf)
+    idx = np.arange(n)
+    with np.errstate(all="ignore"):
+        for k in range(b):
+            cand = np.abs(m[:, k:, k])
+            # the kernel's `a > mx` never selects a NaN below the diagonal
+            cand[:, 1:] = np.where(np.isnan(cand[:, 1:]), -1.0, cand[:, 1:])
+            piv = k + np.argmax(cand, axis=1)
+            mx = np.abs(m[idx, piv, k])
+            upd = ~np.isnan(pmin) & ~(mx >= pmin)
+            pmin[upd] = mx[upd]
+            m[mx == 0.0, k, k] = 1.0
+            for a in (m, inv):
+                rk, rp = a[idx, k].copy(), a[idx, piv].copy()
+                a[idx, k], a[idx, piv] = rp, rk
+            d = 1.0 / m[:, k, k]
+            m[:, k, :] *= d[:, None]
+            inv[:, k, :] *= d[:, None]
+            for r in range(b):
+                if r == k:
+                    continue
+                f = m[:, r, k].copy()
+                nz = f != 0.0
+                m[nz, r, :] -= f[nz, None] * m[nz, k, :]
+                inv[nz, r, :] -= f[nz, None] * inv[nz, k, :]
+    return inv, pmin
+
+
 # ---------------------------------------------------------------------- smoothers
 def jacobi_dinv(A, l1: bool = False) -> torch.Tensor:
     """Scalar: 1/(d_i [+ l1 off-row-sum]); block: inverse of each diagonal block
-    (l1 adds the off-diagonal block-row L1 norms to the block diagonal,
-    reference src/solvers/jacobi_l1_solver.cu)."""
+    (a missing one counts as zero), singular blocks by the rule of
+    _gauss_jordan_inv. L1 SIGN RULE (scalar and block, both backends,
+    reference src/solvers/jacobi_l1_solver.cu): component r of the diagonal
+    takes the l1 norm s of the off-diagonal part of its row with its own
+    sign, D_rr + s where D_rr >= 0 and D_rr - s where D_rr < 0."""
     if A.block_dim == 1:
         work_dtype = torch.complex128 if A.values.is_complex() \
             else torch.float64
@@ -150,14 +193,13 @@ def jacobi_dinv(A, l1: bool = False) -> torch.Tensor:
             _real_only(A, "JACOBI_L1 (the l1 diagonal)")
             m = _csr(A)
             abssum = np.abs(m).sum(axis=1).A1 - np.abs(_np(extract_diagonal(A)))
-            d += torch.from_numpy(np.sign(_np(d)) * abssum)
-            # reference uses d_i + sign(d_i)*sum|offdiag|
+            d += torch.from_numpy(np.where(_np(d) >= 0.0, abssum, -abssum))
         d = torch.where(d.abs() > 0, d, torch.ones_like(d))
         return (1.0 / d).to(A.dtype)
     # block
     _real_only(A, "a block matrix (block Jacobi diagonal)")
     b = A.block_dim
-    D = extract_diagonal(A).double().clone()  # (n, b, b)
+    D = _np(extract_diagonal(A)).astype(np.float64)  # (n, b, b)
     if l1:
         vals = _np(A.values)
         ro = _np(A.row_offsets).astype(np.int64)
@@ -167,12 +209,9 @@ def jacobi_dinv(A, l1: bool = False) -> torch.Tensor:
             for k in range(ro[i], ro[i + 1]):
                 if ci[k] != i:
                     add[i] += np.abs(vals[k]).sum(axis=1)
-        D += torch.diag_embed(torch.from_numpy(add))
-    # guard singular blocks
-    eye = torch.eye(b, dtype=torch.float64).expand_as(D)
-    sing = torch.linalg.matrix_rank(D) < b
-    D = torch.where(sing.view(-1, 1, 1), eye, D)
-    return torch.linalg.inv(D).to(A.dtype)
+        r = np.arange(b)
+        D[:, r, r] += np.where(D[:, r, r] >= 0.0, add, -add)
+    return torch.from_numpy(_gauss_jordan_inv(D)[0]).to(A.dtype)
 
 
 def jacobi_smooth(A, dinv, b, x_in, x_out, omega: float):
@@ -720,27 +759,57 @@ def dilu_setup(A, coloring):
     ci = _np(A.col_indices).astype(np.int64)
     vals = _np(A.values).astype(np.float64)
     D = _np(extract_diagonal(A)).astype(np.float64).copy()
+    has_diag = _np(A.diag_index()) >= 0
+    tau = dilu_pivot_floor(A.dtype)
     # transpose value lookup
     AT = transpose_block_index(A)
     einv = np.zeros_like(D)
-    for c in range(coloring.num_colors):
-        rows = np.nonzero(colors == c)[0]
-        for i in rows:
-            E = D[i].copy()
-            for k in range(ro[i], ro[i + 1]):
-                j = ci[k]
-                # halo columns (j >= n_rows) carry no local Einv: DILU is
-                # rank-local, like the reference's per-partition smoother
-                if j != i and j < A.n_rows and colors[j] < c and AT[k] >= 0:
-                    E -= vals[k] @ einv[j] @ vals[AT[k]]
-            Dref = D[i] if np.abs(np.diag(D[i])).min() > 0 \
-                else np.eye(A.block_dim)
-            if not np.isfinite(E).all() \
-                    or abs(np.linalg.det(E)) < 1e-10 * max(
-                        abs(np.linalg.det(Dref)), 1e-300):
-                E = Dref          # stabilized fallback to the block diagonal
-            einv[i] = np.linalg.inv(E)
+    with np.errstate(all="ignore"):
+        for c in range(coloring.num_colors):
+            rows = np.nonzero(colors == c)[0]
+            for i in rows:
+                E = D[i].copy()
+                for k in range(ro[i], ro[i + 1]):
+                    j = ci[k]
+                    # halo columns (j >= n_rows) carry no local Einv: DILU
+                    # is rank-local, like the reference's per-partition
+                    # smoother
+                    if j != i and j < A.n_rows and colors[j] < c \
+                            and AT[k] >= 0:
+                        E -= vals[k] @ einv[j] @ vals[AT[k]]
+                einv[i] = _dilu_block_inverse(
+                    E, D[i] if has_diag[i] else None, tau)
     return torch.from_numpy(einv).to(A.dtype)
+
+
+def dilu_pivot_floor(dtype) -> float:
+    """Relative pivot floor of the block DILU fallback for matrix values of
+    `dtype`; dilu_pivot_floor of csrc/common.h."""
+    return 1e-5 if dtype in (torch.float32, np.float32) else 1e-10
+
+
+def _dilu_block_inverse(E, D, tau):
+    """Einv_i of block DILU from the modified block E = D_i - sum (...); D is
+    the stored diagonal block or None (then D_i counts as zero).
+    BLOCK DILU FALLBACK RULE (this function, dilu_setup_block and
+    dilu_setup_b4_kernel): E is inverted by the Gauss-Jordan pass of
+    _gauss_jordan_inv; with dmax the largest magnitude in D_i, the result is
+    kept only if
+        max|E| <= 1e10 (dmax + 1)    and
+        min_k |pivot_k| >= tau * (dmax if dmax > 0 else 1),
+    both written so that a NaN fails them. That rejects a non-finite E, one
+    grown wildly through a bad earlier pivot, and one singular to working
+    precision. Otherwise Einv_i is the inverse, by the same pass, of D_i, or
+    the identity where no diagonal block is stored."""
+    dmax = float(np.abs(D).max()) if D is not None else 0.0
+    emax = float(np.fmax.reduce(np.abs(E).ravel(), initial=0.0))
+    inv, pmin = _gauss_jordan_inv(E[None])
+    if emax <= 1e10 * (dmax + 1.0) \
+            and pmin[0] >= tau * (dmax if dmax > 0.0 else 1.0):
+        return inv[0]
+    if D is None:
+        return np.eye(E.shape[0])
+    return _gauss_jordan_inv(D[None])[0][0]
 
 
 def transpose_block_index(A) -> np.ndarray:
@@ -888,7 +957,10 @@ def _ilu0_setup_block(A, coloring):
             k = ci[kidx]
             if pk >= pos[i]:
                 continue
-            ukk_inv = _block_inv(vals[lut[(k, k)]])
+            # a pivot row without a stored diagonal block has a unit one,
+            # as in ilu0_invert_diag_block and in the apply below
+            ukk_inv = _block_inv(vals[lut[(k, k)]]) if (k, k) in lut \
+                else np.eye(b)
             lik = vals[kidx] @ ukk_inv
             vals[kidx] = lik
             for k2 in range(ro[k], ro[k + 1]):

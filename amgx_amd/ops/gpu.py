@@ -50,6 +50,20 @@ def _scratch(A, name, numel, dtype=None):
     return t
 
 
+MAX_BLOCK_DIM = 16
+
+
+def _check_block_dim(A, name):
+    """The block Jacobi / GS / DILU / ILU(0) kernels keep a block, or one
+    vector of block_dim components, in private arrays of MAX_BLOCK_DIM
+    (csrc/core_api.h); refuse a larger block size before anything is
+    launched. The block SpMV takes any block size."""
+    if not 1 <= A.block_dim <= MAX_BLOCK_DIM:
+        raise ValueError(
+            f"{name}: block_dim {A.block_dim} is outside the supported range "
+            f"1..{MAX_BLOCK_DIM} of the block smoother kernels")
+
+
 # ---------------------------------------------------------------------- structure
 def compute_diag_index(A):
     return _didx(A)
@@ -162,6 +176,7 @@ def scal(x, alpha):
 
 # ---------------------------------------------------------------------- smoothers
 def jacobi_dinv(A, l1: bool = False):
+    _check_block_dim(A, "jacobi_dinv")
     if l1 and A.values.is_complex():
         raise NotImplementedError(
             "JACOBI_L1 is not available in the complex modes (dZZI / dCCI / "
@@ -178,6 +193,7 @@ def jacobi_smooth(A, dinv, b, x_in, x_out, omega: float):
 
 
 def gs_smooth_color(A, dinv, b, x, color_rows, omega: float):
+    _check_block_dim(A, "gs_smooth_color")
     _core.gs_smooth_rows(A.row_offsets, A.col_indices, A.values, A.block_dim,
                          dinv, b.reshape(-1), x.reshape(-1), color_rows,
                          float(omega))
@@ -185,6 +201,7 @@ def gs_smooth_color(A, dinv, b, x, color_rows, omega: float):
 
 
 def gs_sweep(A, dinv, b, x, coloring, omega: float, symmetric: bool = False):
+    _check_block_dim(A, "gs_sweep")
     if A.block_dim == 1:
         # color-sorted slab layout (reference reorder-by-color)
         st = _slabs(A, coloring)
@@ -330,6 +347,7 @@ def _check_dilu_coloring(A, coloring):
 
 
 def dilu_setup(A, coloring):
+    _check_block_dim(A, "dilu_setup")
     if A.values.is_complex():
         _check_dilu_coloring(A, coloring)
     einv = _core.dilu_setup(A.row_offsets, A.col_indices, A.values,
@@ -363,6 +381,7 @@ def _dilu_sorted(A, Einv, coloring, rhs, x, relaxation, fused, lanes=0,
     the size, "small_full" being the one-launch apply in its earlier
     full-slab form and "stream" the per-color sweeps in their stream form for
     every color (it goes with lanes=0 only)."""
+    _check_block_dim(A, "dilu_solve / dilu_smooth")
     n = A.n_cols * A.block_dim   # ext size: halo tails stay zero in the sweeps
     w = _scratch(A, "dilu_w", n, x.dtype)   # vector precision (dDFI mixed)
     st = _slabs(A, coloring)
@@ -717,6 +736,7 @@ def interp_d1(A, S, cf_map, num_coarse):
 
 # ---------------------------------------------------------------------- ILU(0)
 def ilu0_setup(A, coloring):
+    _check_block_dim(A, "ilu0_setup")
     pos = _slabs(A, coloring).slot_of_row
     if A.block_dim != 1:
         lu, dinv = _core.ilu0_setup_block(
@@ -751,6 +771,7 @@ def ilu1_pattern(A, coloring):
 
 
 def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):
+    _check_block_dim(A, "ilu0_solve")
     n = A.n_cols * A.block_dim
     y = _scratch(A, "ilu_y", n, r.dtype)    # vector precision (dDFI mixed)
     z = _scratch(A, "ilu_z", n, r.dtype)
