@@ -367,6 +367,13 @@ class MatrixColoring:
     def __init__(self, colors: torch.Tensor, num_colors: int):
         self.colors = colors
         self.num_colors = num_colors
+        if colors.is_cuda:
+            # one native pass: stable order by color and the color bounds
+            from ..ops import gpu
+            self.rows_sorted, self.bounds_dev = gpu.color_order(colors,
+                                                                num_colors)
+            self.bounds = self.bounds_dev.cpu().tolist()
+            return
         counts = torch.bincount(colors.to(torch.int64), minlength=num_colors)
         order = torch.argsort(colors.to(torch.int64), stable=True)
         self.rows_sorted = order.to(torch.int32).contiguous()

@@ -111,7 +111,13 @@ class AggregationLevel(AMGLevel):
 
     def _build_r_structure(self):
         """Aggregate-CSR (offsets, fine ids sorted by aggregate) for
-        deterministic restriction."""
+        deterministic restriction; the Galerkin product of a device level
+        takes the same pair."""
+        if self.aggregates.is_cuda:
+            from ..ops import gpu
+            self.r_structure = gpu.aggregate_csr(self.aggregates,
+                                                 self.num_aggregates)
+            return
         agg = self.aggregates.to(torch.int64)
         order = torch.argsort(agg, stable=True).to(torch.int32)
         counts = torch.bincount(agg, minlength=self.num_aggregates)
@@ -126,7 +132,9 @@ class AggregationLevel(AMGLevel):
         gen = self.scope.get("coarseAgenerator")
         if mgr is None:
             Ac = ops.galerkin_aggregation(self.A, self.aggregates,
-                                          self.num_aggregates, generator=gen)
+                                          self.num_aggregates, generator=gen,
+                                          structure=getattr(
+                                              self, "r_structure", None))
             Ac = self._color_renumber(Ac)
             geom = self.A._cache.get("geometry")
             if geom is not None:
@@ -210,7 +218,8 @@ class AggregationLevel(AMGLevel):
         Ac2 = ops.galerkin_aggregation(self.A, self.aggregates,
                                        self.num_aggregates,
                                        generator=self.scope.get(
-                                           "coarseAgenerator"))
+                                           "coarseAgenerator"),
+                                       structure=self.r_structure)
         # colors in the new numbering are ascending by construction
         self._coarse_coloring = MatrixColoring(
             col.colors[perm].contiguous(), col.num_colors)
@@ -224,7 +233,9 @@ class AggregationLevel(AMGLevel):
         Ac = ops.galerkin_aggregation(self.A, self.aggregates,
                                       self.num_aggregates,
                                       generator=self.scope.get(
-                                          "coarseAgenerator"))
+                                          "coarseAgenerator"),
+                                      structure=getattr(self, "r_structure",
+                                                        None))
         # aggregates already carry the color renumbering; re-attach the
         # structure-valid coloring so sweeps keep the identity ordering
         coloring = getattr(self, "_coarse_coloring", None)

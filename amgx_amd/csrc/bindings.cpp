@@ -760,61 +760,181 @@ void dilu_small(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
     });
 }
 
+// ---------------------------------------------------------------- round loops
+// The coloring and matching loops end when a round reports nothing left /
+// nothing changed. Each round writes its own int32 slot of an array zeroed
+// once per call, and the host reads the slots back once per batch of k
+// rounds. That is sound because a round past the end is a no-op: a coloring
+// round on a fully colored graph copies the colors, a matching round after
+// one that formed no pair sees the same state and forms none. A surplus
+// round still streams the level, so k shrinks as the level grows:
+// k = 8 up to 2^18 rows, then 4, 2, and 1 from 2^22 rows (profiles/NOTES.md,
+// "Setup round loops").
+constexpr int64_t ROUND_SLOTS = 512;
+int64_t round_batch(int64_t n, int64_t batch) {
+    TORCH_CHECK(batch >= 0, "batch must be 0 (by level size) or positive");
+    if (batch > 0) return std::min(batch, ROUND_SLOTS);
+    if (n >= (int64_t(1) << 22)) return 1;
+    if (n >= (int64_t(1) << 20)) return 2;
+    if (n >= (int64_t(1) << 18)) return 4;
+    return 8;
+}
+
+// Runs round(r, slot) for r = 0, 1, ... in batches of k until a round leaves
+// its slot at 0 or max_rounds have run; true when a round did. The rounds
+// run may exceed the deciding one by up to k - 1.
+template <typename Round>
+bool run_rounds(int64_t max_rounds, int64_t k, const Tensor& like,
+                Round round) {
+    auto slots = torch::zeros({ROUND_SLOTS},
+                              like.options().dtype(torch::kInt32));
+    int64_t rounds = 0, used = 0;
+    while (rounds < max_rounds) {
+        int64_t kk = std::min(k, max_rounds - rounds);
+        if (used + kk > ROUND_SLOTS) {   // the batch before has been read back
+            slots.zero_();
+            used = 0;
+        }
+        for (int64_t r = 0; r < kk; ++r, ++rounds)
+            round(rounds, iptr(slots) + used + r);
+        auto host = slots.narrow(0, used, kk).cpu();
+        const int* h = host.data_ptr<int>();
+        for (int64_t r = 0; r < kk; ++r)
+            if (h[r] == 0) return true;
+        used += kk;
+    }
+    return false;
+}
+
 // ---------------------------------------------------------------- coloring
 // mode 0: greedy smallest-unused color (MIN_MAX / PARALLEL_GREEDY class);
 // mode 1: MULTI_HASH — `mode1_rounds` rounds assigning color = round id
 // with per-round re-hash, then greedy cleanup rounds for leftovers.
+// batch: rounds per read-back, 0 = by level size (round_batch); the colors
+// are the same for every value.
 std::tuple<Tensor, int64_t> color_minmax(Tensor ro, Tensor ci, int64_t n,
                                          int64_t max_rounds, int64_t seed,
-                                         int64_t mode1_rounds) {
+                                         int64_t mode1_rounds, int64_t batch) {
+    check_dev(ro);
+    TORCH_CHECK(ro.numel() == n + 1, "color_minmax: ro does not have n rows");
     auto colors = torch::full({n}, -1,
                               ro.options().dtype(torch::kInt32));
+    if (n == 0) return {colors, 0};
     auto colors_next = torch::empty_like(colors);
-    auto counter = torch::zeros({1}, ro.options().dtype(torch::kInt32));
     hipStream_t st = cur_stream();
-    int rounds = 0;
-    for (; rounds < max_rounds; ++rounds) {
-        counter.zero_();
-        int mode = rounds < mode1_rounds ? 1 : 0;
-        amgx_hip::color_minmax_round(
-            iptr(ro), iptr(ci), (int)n, iptr(colors), iptr(colors_next),
-            rounds, (int)(seed + rounds * 7919), mode, iptr(counter), st);
-        std::swap(colors, colors_next);
-        int left = counter.cpu().item<int>();
-        if (left == 0) break;
-    }
-    TORCH_CHECK((colors.min().cpu().item<int>()) >= 0,
-                "MIN_MAX coloring did not converge in ", max_rounds,
+    bool done = run_rounds(
+        max_rounds, round_batch(n, batch), ro, [&](int64_t r, int* left) {
+            int mode = r < mode1_rounds ? 1 : 0;
+            amgx_hip::color_minmax_round(
+                iptr(ro), iptr(ci), (int)n, iptr(colors), iptr(colors_next),
+                (int)r, (int)(seed + r * 7919), mode, left, st);
+            std::swap(colors, colors_next);
+        });
+    // a round that left no row uncolored is the convergence check
+    TORCH_CHECK(done, "MIN_MAX coloring did not converge in ", max_rounds,
                 " rounds");
-    int64_t ncolors = (colors.max().cpu().item<int>()) + 1;
+    auto top = torch::zeros({1}, ro.options().dtype(torch::kInt32));
+    amgx_hip::int_max(iptr(colors), (int)n, iptr(top), st);
+    int64_t ncolors = top.cpu().item<int>() + 1;
     return {colors, ncolors};
 }
 
 // ---------------------------------------------------------------- aggregation
+// batch: handshake rounds per read-back, 0 = by level size (round_batch).
+// weights: the propose kernel reads edge weights computed once per call
+// (one double per entry) instead of computing them from va, tidx and diag in
+// every round. The roots are the same for every value of either.
 Tensor size2_match(Tensor ro, Tensor ci, Tensor va, Tensor tidx, Tensor diag,
-                   int64_t n, int64_t max_iters, int64_t seed) {
+                   int64_t n, int64_t max_iters, int64_t seed,
+                   int64_t batch, bool weights) {
     auto agg = torch::full({n}, -1, ro.options().dtype(torch::kInt32));
+    if (n == 0) return agg;
     auto prop = torch::empty({n}, ro.options().dtype(torch::kInt32));
-    auto changed = torch::zeros({1}, ro.options().dtype(torch::kInt32));
     hipStream_t st = cur_stream();
     DISPATCH(AMGX_VALUE_TYPES, "size2_match", (va), [&] {
-        for (int it = 0; it < max_iters; ++it) {
+        Tensor w;
+        const double* wpre = nullptr;
+        if (weights) {
+            w = torch::empty({ci.numel()},
+                             ro.options().dtype(torch::kFloat64));
+            amgx_hip::agg_edge_weights<scalar_t>(
+                iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
+                dptr<scalar_t>(diag), (int)n, dptr<double>(w), st);
+            wpre = dptr<double>(w);
+        }
+        run_rounds(max_iters, round_batch(n, batch), ro,
+                   [&](int64_t, int* changed) {
             amgx_hip::agg_propose<scalar_t>(
                 iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
-                dptr<scalar_t>(diag), (int)n, iptr(agg), iptr(prop), (int)seed,
-                st);
-            changed.zero_();
-            amgx_hip::agg_match(iptr(prop), (int)n, iptr(agg), iptr(changed),
-                                st);
-            if (changed.cpu().item<int>() == 0) break;
-        }
+                dptr<scalar_t>(diag), wpre, (int)n, iptr(agg), iptr(prop),
+                (int)seed, st);
+            amgx_hip::agg_match(iptr(prop), (int)n, iptr(agg), changed, st);
+        });
         auto agg_out = torch::empty_like(agg);
         amgx_hip::agg_merge_singletons<scalar_t>(
             iptr(ro), iptr(ci), dptr<scalar_t>(va), iptr(tidx),
             dptr<scalar_t>(diag), (int)n, iptr(agg), iptr(agg_out), st);
         agg = agg_out;
     });
-    return agg;   // root fine-node ids; Python renumbers with torch.unique
+    return agg;   // root fine-node ids; size2_renumber numbers them
+}
+
+// roots of size2_match -> (agg int32[n], num): consecutive ids in ascending
+// root order, the values of torch.unique(roots, sorted, return_inverse)
+std::tuple<Tensor, int64_t> size2_renumber(Tensor roots) {
+    check_dev(roots);
+    int64_t n = roots.numel();
+    auto agg = torch::empty({n}, roots.options());
+    auto ids = torch::empty({n + 1}, roots.options());
+    amgx_hip::root_renumber(iptr(roots), (int)n, iptr(ids), iptr(agg),
+                            cur_stream());
+    int64_t num = ids[n].cpu().item<int>();
+    return {agg, num};
+}
+
+// Stable order of the rows by an int32 key in [0, nkeys): (order int32[n],
+// offsets int32[nkeys + 1]), the values of argsort(stable) and of bincount +
+// cumsum. Serves the color order (keys = colors) and the aggregate-membership
+// CSR (keys = aggregate ids).
+std::tuple<Tensor, Tensor> key_order(Tensor keys, int64_t nkeys) {
+    check_dev(keys);
+    TORCH_CHECK(nkeys >= 0 && nkeys < INT_MAX && keys.numel() < INT_MAX,
+                "key_order: sizes out of the int32 range");
+    int64_t n = keys.numel();
+    auto order = torch::empty({n}, keys.options());
+    auto off = torch::empty({std::max<int64_t>(nkeys, 1) + 1}, keys.options());
+    amgx_hip::key_order(iptr(keys), (int)n, (int)nkeys, iptr(order),
+                        iptr(off), cur_stream());
+    return {order, off.narrow(0, 0, nkeys + 1)};
+}
+
+// Slab structure under the row order rows_sorted: (ro_s int32[n + 1],
+// ci_s int32[nnz], nzmap int32[nnz], slot_of_row int32[n]). lanes: lanes per
+// row of the fill, 0 = by entries per row as the full-slab sweeps.
+std::vector<Tensor> slab_structure(Tensor ro, Tensor ci, Tensor rows_sorted,
+                                   int64_t lanes) {
+    check_dev(ro);
+    int64_t n = (int64_t)ro.numel() - 1, nnz = ci.numel();
+    TORCH_CHECK(rows_sorted.numel() == n,
+                "slab_structure: rows_sorted does not have n rows");
+    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
+                "slab_structure: lanes must be 0 (routed), 1 or 8");
+    hipStream_t st = cur_stream();
+    auto ro_s = torch::empty({n + 1}, ro.options());
+    auto slot = torch::empty({n}, ro.options());
+    long long total = amgx_hip::slab_offsets(iptr(ro), iptr(rows_sorted),
+                                             (int)n, iptr(ro_s), iptr(slot),
+                                             st);
+    TORCH_CHECK(total == nnz, "slab_structure: rows_sorted is no permutation "
+                "of the rows (", total, " entries of ", nnz, ")");
+    auto nzmap = torch::empty({nnz}, ro.options());
+    auto ci_s = torch::empty({nnz}, ro.options());
+    if (lanes == 0)
+        lanes = dilu_lanes((double)nnz / (double)std::max<int64_t>(n, 1),
+                           false);
+    amgx_hip::slab_fill(iptr(ro), iptr(ci), iptr(rows_sorted), (int)n,
+                        (int)lanes, iptr(ro_s), iptr(nzmap), iptr(ci_s), st);
+    return {ro_s, ci_s, nzmap, slot};
 }
 
 // MULTI_PAIRWISE edge weights, one double per stored entry
@@ -1317,8 +1437,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.attr("DILU_STREAM_MIN_ROWS_FULL") = DILU_STREAM_MIN_ROWS_FULL;
     m.attr("DILU_STREAM_MIN_ROWS_SPLIT") = DILU_STREAM_MIN_ROWS_SPLIT;
     m.def("slab_split", &slab_split);
-    m.def("color_minmax", &color_minmax);
-    m.def("size2_match", &size2_match);
+    {
+        using pybind11::arg;
+        m.def("color_minmax", &color_minmax, arg("ro"), arg("ci"), arg("n"),
+              arg("max_rounds"), arg("seed"), arg("mode1_rounds"),
+              arg("batch") = 0);
+        m.def("size2_match", &size2_match, arg("ro"), arg("ci"), arg("va"),
+              arg("tidx"), arg("diag"), arg("n"), arg("max_iters"),
+              arg("seed"), arg("batch") = 0, arg("weights") = false);
+        m.def("slab_structure", &slab_structure, arg("ro"), arg("ci"),
+              arg("rows_sorted"), arg("lanes") = 0);
+    }
+    m.def("size2_renumber", &size2_renumber);
+    m.def("key_order", &key_order);
     m.def("pairwise_weights", &pairwise_weights);
     m.def("pairwise_propose", &pairwise_propose);
     m.def("pairwise_match", &pairwise_match);

@@ -276,18 +276,28 @@ void dilu_setup_b4(const int* ro, const int* ci, const TA* va,
 
 // ============================================================ kernels_setup.hip
 // ---- coloring --------------------------------------------------------------
-// one min-max hash round; returns (via counter) number newly colored.
+// one min-max hash round; *left (zeroed by the caller) becomes 1 when a row
+// stays uncolored. A round on a fully colored graph copies the colors.
 void color_minmax_round(const int* ro, const int* ci, int n,
                         const int* colors_prev, int* colors_next, int iter,
-                        int seed, int mode, int* n_uncolored, hipStream_t s);
+                        int seed, int mode, int* left, hipStream_t s);
+// *out = max(*out, v[0..n))
+void int_max(const int* v, int n, int* out, hipStream_t s);
 
 // ---- aggregation -----------------------------------------------------------
 // agg_propose / agg_merge_singletons: [value]; the edge weight of a complex
 // entry is its modulus, taken in double
+// wpre: the weights of agg_edge_weights (one double per entry), or nullptr to
+// compute each weight from va, tidx and diag; the same proposals either way
 template <typename T>
 void agg_propose(const int* ro, const int* ci, const T* va, const int* tidx,
-                 const T* diag, int n, const int* agg, int* prop, int seed,
-                 hipStream_t s);
+                 const T* diag, const double* wpre, int n, const int* agg,
+                 int* prop, int seed, hipStream_t s);
+template <typename T>
+void agg_edge_weights(const int* ro, const int* ci, const T* va,
+                      const int* tidx, const T* diag, int n, double* w,
+                      hipStream_t s);
+// *changed (zeroed by the caller) becomes 1 when the round forms a pair
 void agg_match(const int* prop, int n, int* agg, int* changed, hipStream_t s);
 template <typename T>
 void agg_merge_singletons(const int* ro, const int* ci, const T* va,
@@ -335,6 +345,29 @@ void pairwise_renumber(int* agg, int n, const int* sizes_in, int* ids,
                        void* tmp, size_t tmp_bytes, int* agg_out,
                        int* sizes_out, hipStream_t s);
 
+// ============================================================ kernels_order.hip
+// Stable order of n rows by an int32 key in [0, nkeys): order (n) = rows
+// sorted by key, ascending within a key; off (nkeys + 1) = first position of
+// each key, off[nkeys] = n. The values of torch.argsort(stable=True) and of
+// bincount + cumsum, from one radix sort over the key bits in use.
+void key_order(const int* keys, int n, int nkeys, int* order, int* off,
+               hipStream_t s);
+// Matching roots (roots[r] == r exactly at the roots) to consecutive ids in
+// ascending root order: agg[i] = id of roots[i]. ids: n + 1 ints of scratch,
+// ids[n] = number of roots afterwards. No sort.
+void root_renumber(const int* roots, int n, int* ids, int* agg,
+                   hipStream_t s);
+// Structure of the slab whose row t is row rows[t] of (ro, ci).
+// slab_offsets: ro_s (n + 1) and slot_of_row (n, inverse of rows); returns
+// ro_s[n] (one host sync). slab_fill: nzmap[ro_s[t] + e] = ro[rows[t]] + e
+// and ci_s = ci[nzmap], by 1 or 8 lanes per row.
+long long slab_offsets(const int* ro, const int* rows, int n, int* ro_s,
+                       int* slot_of_row, hipStream_t s);
+void slab_fill(const int* ro, const int* ci, const int* rows, int n,
+               int lanes, const int* ro_s, int* nzmap, int* ci_s,
+               hipStream_t s);
+
+// ============================================================ kernels_setup.hip
 // ---- strict color-split of a color-sorted slab -------------------------------
 // The U (upper) / L part of slot t keeps, in slab order, the entries with a
 // local column j < n of a later / earlier color than the row's; diagonal,

@@ -13,6 +13,7 @@
 // rocPRIM is used only for device sort/scan/reduce primitives (design
 // stance: SURVEY.md §7 — math kernels hand-written, rocPRIM for utilities).
 
+#include <climits>
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -50,56 +51,89 @@ __device__ __forceinline__ unsigned int hash_u32(unsigned int a,
 // neighbor decisions must be invisible, or the result depends on wave
 // scheduling — valid but nondeterministic (host model's frozen-snapshot
 // semantics; determinism_flag discipline, reference src/core.cu:313).
+// The round reports "a row is still uncolored" through *left, which the
+// caller zeroes: the workgroup votes and one thread stores the constant 1, and
+// only while it still reads 0, so the shared word sees a handful of plain
+// stores per round instead of one read-modify-write per losing row. Every
+// thread reaches the vote: no return stands ahead of it.
 __global__ __launch_bounds__(AMGX_BLOCK) void color_round_kernel(const int* __restrict__ ro,
                                    const int* __restrict__ ci, int n,
                                    const int* __restrict__ colors_prev,
                                    int* __restrict__ colors_next, int iter,
-                                   int seed, int mode,
-                                   int* __restrict__ n_uncolored) {
+                                   int seed, int mode, int* left) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (colors_prev[i] >= 0) { colors_next[i] = colors_prev[i]; return; }
-    unsigned long long mine =
-        ((unsigned long long)hash_u32((unsigned)i, (unsigned)seed) << 32) |
-        (unsigned)i;
-    bool is_max = true;
-    unsigned long long used = 0ull;
-    int big_used_max = -1;
-    for (int k = ro[i]; k < ro[i + 1]; ++k) {
-        int j = ci[k];
-        if (j == i || j >= n) continue;
-        int cj = colors_prev[j];
-        if (cj >= 0) {
-            if (cj < 64) used |= (1ull << cj);
-            else big_used_max = max(big_used_max, cj);
-            continue;
+    int lost = 0;
+    if (i < n) {
+        int out = colors_prev[i];
+        if (out < 0) {
+            unsigned long long mine =
+                ((unsigned long long)hash_u32((unsigned)i, (unsigned)seed) << 32) |
+                (unsigned)i;
+            bool is_max = true;
+            unsigned long long used = 0ull;
+            int big_used_max = -1;
+            for (int k = ro[i]; k < ro[i + 1]; ++k) {
+                int j = ci[k];
+                if (j == i || j >= n) continue;
+                int cj = colors_prev[j];
+                if (cj >= 0) {
+                    if (cj < 64) used |= (1ull << cj);
+                    else big_used_max = max(big_used_max, cj);
+                    continue;
+                }
+                unsigned long long h =
+                    ((unsigned long long)hash_u32((unsigned)j, (unsigned)seed) << 32) |
+                    (unsigned)j;
+                if (h > mine) { is_max = false; break; }
+            }
+            if (is_max) {
+                if (mode == 1) {
+                    out = iter;
+                } else {
+                    int c = (int)(__builtin_ffsll((long long)~used) - 1);
+                    // beyond-bitmask: colors 0..63 are all taken
+                    if (c < 0 || c >= 64) c = max(big_used_max, 63) + 1;
+                    out = c;
+                }
+            } else {
+                lost = 1;
+            }
         }
-        unsigned long long h =
-            ((unsigned long long)hash_u32((unsigned)j, (unsigned)seed) << 32) |
-            (unsigned)j;
-        if (h > mine) { is_max = false; break; }
+        colors_next[i] = out;
     }
-    int out = -1;
-    if (is_max) {
-        if (mode == 1) {
-            out = iter;
-        } else {
-            int c = (int)(__builtin_ffsll((long long)~used) - 1);
-            if (c < 0 || c >= 64) c = big_used_max + 1;  // beyond-bitmask
-            out = c;
-        }
-    } else {
-        atomicAdd(n_uncolored, 1);
-    }
-    colors_next[i] = out;
+    if (__syncthreads_or(lost) && threadIdx.x == 0 && *left == 0) *left = 1;
 }
 
 void color_minmax_round(const int* ro, const int* ci, int n,
                         const int* colors_prev, int* colors_next, int iter,
-                        int seed, int mode, int* n_uncolored, hipStream_t s) {
+                        int seed, int mode, int* left, hipStream_t s) {
     hipLaunchKernelGGL(color_round_kernel, dim3(grid_1d(n)), dim3(AMGX_BLOCK),
                        0, s, ro, ci, n, colors_prev, colors_next, iter, seed,
-                       mode, n_uncolored);
+                       mode, left);
+}
+
+// *out = max(*out, max of v[0..n)): one atomic per workgroup of a capped grid
+__global__ __launch_bounds__(AMGX_BLOCK) void int_max_kernel(
+    const int* __restrict__ v, int n, int* __restrict__ out) {
+    int m = INT_MIN;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x)
+        m = max(m, v[i]);
+    __shared__ int lds[AMGX_BLOCK];
+    lds[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = AMGX_BLOCK / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            lds[threadIdx.x] = max(lds[threadIdx.x], lds[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(out, lds[0]);
+}
+
+void int_max(const int* v, int n, int* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(int_max_kernel, dim3(grid_1d(n, AMGX_BLOCK, 1024)),
+                       dim3(AMGX_BLOCK), 0, s, v, n, out);
 }
 
 // ============================================================ aggregation
@@ -118,12 +152,31 @@ __device__ __forceinline__ double edge_weight(const T* va, const int* tidx,
     return (aij + aji) * scale;
 }
 
+// The weight of every entry once per level (0 where the propose kernel never
+// asks: diagonal and halo columns), for the PRE form of the propose kernel.
+// The expression is edge_weight itself, so both forms compare the same bits.
 template <typename T>
+__global__ __launch_bounds__(AMGX_BLOCK) void agg_edge_weights_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const T* __restrict__ va, const int* __restrict__ tidx,
+    const T* __restrict__ diag, int n, double* __restrict__ w) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int k = ro[i]; k < ro[i + 1]; ++k) {
+        int j = ci[k];
+        w[k] = (j == i || j >= n) ? 0.0 : edge_weight(va, tidx, diag, k, i, j);
+    }
+}
+
+// PRE: read the weight of an entry from wpre (agg_edge_weights_kernel)
+// instead of computing it from va, tidx and diag.
+template <typename T, bool PRE>
 __global__ __launch_bounds__(AMGX_BLOCK) void agg_propose_kernel(const int* __restrict__ ro,
                                    const int* __restrict__ ci,
                                    const T* __restrict__ va,
                                    const int* __restrict__ tidx,
-                                   const T* __restrict__ diag, int n,
+                                   const T* __restrict__ diag,
+                                   const double* __restrict__ wpre, int n,
                                    const int* __restrict__ agg,
                                    int* __restrict__ prop, int seed) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,7 +188,7 @@ __global__ __launch_bounds__(AMGX_BLOCK) void agg_propose_kernel(const int* __re
     for (int k = ro[i]; k < ro[i + 1]; ++k) {
         int j = ci[k];
         if (j == i || j >= n || agg[j] >= 0) continue;
-        double w = edge_weight(va, tidx, diag, k, i, j);
+        double w = PRE ? wpre[k] : edge_weight(va, tidx, diag, k, i, j);
         // Weight ties broken by a seeded per-node hash key (mirrors the host
         // path's random tie[] and the reference's hashed weights,
         // src/aggregation/selectors/size2_selector.cu) — a pure row-id
@@ -152,17 +205,22 @@ __global__ __launch_bounds__(AMGX_BLOCK) void agg_propose_kernel(const int* __re
     prop[i] = best;
 }
 
+// *changed (zeroed by the caller) becomes 1 when the round forms a pair: a
+// workgroup vote and one plain store, as color_round_kernel.
 __global__ __launch_bounds__(AMGX_BLOCK) void agg_match_kernel(const int* __restrict__ prop, int n,
-                                 int* __restrict__ agg,
-                                 int* __restrict__ changed) {
+                                 int* __restrict__ agg, int* changed) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int j = prop[i];
-    if (j >= 0 && prop[j] == i && i < j) {
-        agg[i] = i;   // root id = smaller partner
-        agg[j] = i;
-        atomicAdd(changed, 1);
+    int made = 0;
+    if (i < n) {
+        int j = prop[i];
+        if (j >= 0 && prop[j] == i && i < j) {
+            agg[i] = i;   // root id = smaller partner
+            agg[j] = i;
+            made = 1;
+        }
     }
+    if (__syncthreads_or(made) && threadIdx.x == 0 && *changed == 0)
+        *changed = 1;
 }
 
 template <typename T>
@@ -191,12 +249,22 @@ __global__ __launch_bounds__(AMGX_BLOCK) void agg_singleton_kernel(const int* __
 }
 
 template <typename T>
+void agg_edge_weights(const int* ro, const int* ci, const T* va,
+                      const int* tidx, const T* diag, int n, double* w,
+                      hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL((agg_edge_weights_kernel<T>), dim3(grid_1d(n)),
+                       dim3(AMGX_BLOCK), 0, s, ro, ci, va, tidx, diag, n, w);
+}
+
+template <typename T>
 void agg_propose(const int* ro, const int* ci, const T* va, const int* tidx,
-                 const T* diag, int n, const int* agg, int* prop, int seed,
-                 hipStream_t s) {
-    hipLaunchKernelGGL((agg_propose_kernel<T>), dim3(grid_1d(n)),
-                       dim3(AMGX_BLOCK), 0, s, ro, ci, va, tidx, diag, n, agg,
-                       prop, seed);
+                 const T* diag, const double* wpre, int n, const int* agg,
+                 int* prop, int seed, hipStream_t s) {
+    auto kern = wpre ? agg_propose_kernel<T, true>
+                     : agg_propose_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(grid_1d(n)), dim3(AMGX_BLOCK), 0, s, ro, ci,
+                       va, tidx, diag, wpre, n, agg, prop, seed);
 }
 
 void agg_match(const int* prop, int n, int* agg, int* changed, hipStream_t s) {
@@ -1063,6 +1131,7 @@ void slab_split_fill(const int* ro_s, const int* ci_s, const int* rows,
 // the transpose serves classical AMG only and stays real
 #define INSTANTIATE_SETUP(T)                                                   \
     AMGX_INSTANTIATE(agg_propose, T)                                           \
+    AMGX_INSTANTIATE(agg_edge_weights, T)                                      \
     AMGX_INSTANTIATE(agg_merge_singletons, T)                                  \
     AMGX_INSTANTIATE(pairwise_weights, T)                                      \
     AMGX_INSTANTIATE(galerkin_agg, T)                                         \

@@ -196,16 +196,20 @@ def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
 
 
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
-                         ncols_mod=None, generator=None):
+                         ncols_mod=None, generator=None, structure=None):
     """Coarse A for piecewise-constant aggregation P:
     Ac[I,J] = sum_{i in I, j in J} A[i,j].
     Reference: src/aggregation/coarseAgenerators/ (LOW_DEG / THRUST).
     agg_col/ncols_mod: distributed variant (GLOBAL coarse column ids).
     generator: None/"LOW_DEG"/"HYBRID" = LDS-hash with one-sort fallback
     (the default tiering IS the HYBRID role); "THRUST" = force the one-sort
-    sort/reduce generator (reference coarseAgenerators/thrust_...)."""
+    sort/reduce generator (reference coarseAgenerators/thrust_...).
+    structure: the aggregate-membership CSR (offsets, fine ids sorted by
+    aggregate) where the caller holds it already, as AggregationLevel does
+    for its restriction; it is built when absent."""
     return _backend(A).galerkin_aggregation(A, aggregates, num_aggregates,
-                                            agg_col, ncols_mod, generator)
+                                            agg_col, ncols_mod, generator,
+                                            structure)
 
 
 def restrict_agg(r, aggregates, num_aggregates, block_dim: int = 1,

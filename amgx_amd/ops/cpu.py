@@ -563,7 +563,8 @@ def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
 
 
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
-                         ncols_mod=None, generator=None):
+                         ncols_mod=None, generator=None, structure=None):
+    # structure: the device path's aggregate CSR; the host product sorts
     # generator: the host path has a single sort/reduce implementation
     # (the THRUST analogue); LOW_DEG/HYBRID map onto it unchanged
     from ..matrix import CSRMatrix

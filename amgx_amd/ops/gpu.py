@@ -205,7 +205,8 @@ def gs_sweep(A, dinv, b, x, coloring, omega: float, symmetric: bool = False):
     if A.block_dim == 1:
         # color-sorted slab layout (reference reorder-by-color)
         st = _slabs(A, coloring)
-        va_s = _slab_copy(st, "gs_va", A.values, lambda v: v[st.nzmap])
+        va_s = _slab_copy(st, "gs_va", A.values,
+                          lambda v: _gather_nz(v, st.nzmap))
         dinv_s = _slab_copy(st, "gs_dinv", dinv,
                             lambda d: d.reshape(-1)[st.perm])
         _core.gs_sweep_sorted(st.ro_s, st.ci_s, va_s, dinv_s, b.reshape(-1),
@@ -220,24 +221,49 @@ def gs_sweep(A, dinv, b, x, coloring, omega: float, symmetric: bool = False):
 
 
 # ---------------------------------------------------------------------- coloring
+# Rounds per read-back of the round flags in the coloring and matching loops
+# where the caller names none: 0 = by level size (bindings.cpp round_batch).
+# Every value gives the same colors and aggregates; tests set it to compare.
+ROUND_BATCH = 0
+
+
 def color_matrix(A, max_uncolored_frac: float = 0.0, seed: int = 0,
-                 multihash_rounds: int = 0):
+                 multihash_rounds: int = 0, batch: int = 0):
     """Device Jones-Plassmann greedy coloring rounds; multihash_rounds > 0
-    prepends MULTI_HASH semantics (color = round id, per-round re-hash)."""
+    prepends MULTI_HASH semantics (color = round id, per-round re-hash).
+    batch (tests, bench_kernels.py): rounds per read-back of the round flags,
+    0 = by level size; every value gives the same colors."""
     # dense coarse-level graphs (classical RAP) need ~max-clique rounds:
     # each greedy round colors only the local maxima of the uncolored set
     colors, nc = _core.color_minmax(A.row_offsets, A.col_indices, A.n_rows,
-                                    4096, int(seed), int(multihash_rounds))
+                                    4096, int(seed), int(multihash_rounds),
+                                    int(batch or ROUND_BATCH))
     return colors, int(nc)
+
+
+def color_order(colors, num_colors):
+    """(rows_sorted int32, bounds_dev int32 (num_colors + 1,)): the rows
+    stably sorted by color and the first slot of each color."""
+    return _core.key_order(colors.to(torch.int32).contiguous(),
+                           int(num_colors))
+
+
+def aggregate_csr(aggregates, num_aggregates):
+    """Aggregate-membership CSR (offsets int32 (num + 1,), fine ids int32
+    sorted by aggregate, ascending within one)."""
+    fids, off = _core.key_order(aggregates.to(torch.int32).contiguous(),
+                                int(num_aggregates))
+    return off, fids
 
 
 # ---------------------------------------------------------------------- DILU
 class _Slabs:
     """Structure of the rows_sorted-gathered matrix copy under ONE coloring
     (reference reorder-by-color, include/matrix.h:766): slot-ordered row
-    offsets ro_s, gathered columns ci_s, the nz gather map nzmap (for value
-    re-gathers after replace_coefficients), perm = rows_sorted as int64 and
-    its inverse slot_of_row; copies holds the gathered value arrays.
+    offsets ro_s, gathered columns ci_s, the int32 nz gather map nzmap (for
+    value re-gathers after replace_coefficients, through _gather_nz),
+    perm = rows_sorted as int64 and its inverse slot_of_row; copies holds the
+    gathered value arrays.
     upper / lower: the strict color-split parts of the slab for the scalar
     DILU sweeps, each (offsets, columns, int32 map into the full slab), built
     on first use by _slab_part."""
@@ -254,25 +280,19 @@ def _slabs(A, coloring):
         st.coloring = coloring
         st.copies = {}
         st.upper = st.lower = None
-        n = A.n_rows
-        perm = coloring.rows_sorted.to(torch.int64)
-        ro64 = A.row_offsets.to(torch.int64)
-        deg = ro64[1:] - ro64[:-1]
-        counts = deg[perm]
-        total = int(A.nnz)
-        st.ro_s = torch.zeros(n + 1, dtype=torch.int32, device=A.device)
-        csum = torch.cumsum(counts, 0)
-        st.ro_s[1:] = csum.to(torch.int32)
-        st.nzmap = (torch.repeat_interleave(ro64[perm], counts)
-                    + torch.arange(total, device=A.device, dtype=torch.int64)
-                    - torch.repeat_interleave(csum - counts, counts))
-        st.ci_s = A.col_indices[st.nzmap].contiguous()
-        st.perm = perm
-        st.slot_of_row = torch.empty(n, dtype=torch.int32, device=A.device)
-        st.slot_of_row[perm] = torch.arange(n, dtype=torch.int32,
-                                            device=A.device)
+        st.ro_s, st.ci_s, st.nzmap, st.slot_of_row = _core.slab_structure(
+            A.row_offsets, A.col_indices, coloring.rows_sorted)
+        st.perm = coloring.rows_sorted.to(torch.int64)
         A._cache["slabs"] = st
     return st
+
+
+def _gather_nz(values, nzmap, b: int = 1):
+    """values[nzmap] for b components per entry, flat."""
+    src = values.reshape(-1)
+    out = torch.empty(nzmap.numel() * b, dtype=src.dtype, device=src.device)
+    _core.gather(src.contiguous(), nzmap, b, out)
+    return out
 
 
 def _slab_copy(st, name, src, gather):
@@ -355,7 +375,7 @@ def dilu_setup(A, coloring):
                             coloring.rows_sorted, coloring.bounds)
     st = _slabs(A, coloring)
     bb = A.block_dim * A.block_dim
-    va_s = A.values.reshape(A.nnz, -1)[st.nzmap].reshape(-1).contiguous()
+    va_s = _gather_nz(A.values, st.nzmap, bb)
     einv_s = einv.reshape(A.n_rows, bb)[st.perm].reshape(-1).contiguous() \
         if A.block_dim > 1 else einv[st.perm].contiguous()
     # scalar levels of every size sweep the U part backwards
@@ -459,8 +479,13 @@ def dilu_solve(A, Einv, coloring, r, relaxation, x, lanes=0, sweeps=1,
 
 
 # ---------------------------------------------------------------------- aggregation
-def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
-                   seed: int = 0):
+def size2_roots(A, max_iterations: int = 15, seed: int = 0, batch: int = 0,
+                weights: bool = False):
+    """The handshake matching as root fine-row ids (int32 (n,); roots[r] == r
+    exactly at the roots). batch (tests, bench_kernels.py): rounds per
+    read-back, 0 = ROUND_BATCH. weights (tests, bench_kernels.py): edge
+    weights computed once per call instead of in every round. Every value of
+    either gives the same roots."""
     if A.block_dim > 1 and A.values.is_complex():
         raise NotImplementedError(
             "aggregation of a block matrix is not available in the complex "
@@ -471,17 +496,23 @@ def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
         diag = torch.linalg.vector_norm(diag.reshape(A.n_rows, -1), dim=1)
         va = torch.linalg.vector_norm(
             A.values.reshape(A.nnz, -1).to(torch.float64), dim=1).to(A.dtype)
-        roots = _core.size2_match(A.row_offsets, A.col_indices, va, _tidx(A),
-                                  diag.to(A.dtype), A.n_rows, max_iterations,
-                                  int(seed) + 0x9E3779B1)
+        diag = diag.to(A.dtype)
     else:
         # scalar, real or complex: the kernel weighs an edge by |a_ij|,
         # the modulus for complex values
-        roots = _core.size2_match(A.row_offsets, A.col_indices, A.values,
-                                  _tidx(A), diag, A.n_rows, max_iterations,
-                                  int(seed) + 0x9E3779B1)
-    uniq, agg = torch.unique(roots, sorted=True, return_inverse=True)
-    return agg.to(torch.int32), int(uniq.numel())
+        va = A.values
+    return _core.size2_match(A.row_offsets, A.col_indices, va, _tidx(A), diag,
+                             A.n_rows, max_iterations,
+                             int(seed) + 0x9E3779B1,
+                             int(batch or ROUND_BATCH), bool(weights))
+
+
+def size2_matching(A, max_iterations: int = 15, deterministic: bool = True,
+                   seed: int = 0, batch: int = 0):
+    # the roots are fine-row ids: flag, scan and map number them, no sort
+    agg, num = _core.size2_renumber(
+        size2_roots(A, max_iterations, seed, batch))
+    return agg, int(num)
 
 
 def pairwise_weights(A, formula: int = 0):
@@ -519,8 +550,11 @@ def pairwise_matching(row_offsets, col_indices, w, n, sizes, cap,
 
 
 def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
-                         ncols_mod=None, generator=None):
-    """agg_col/ncols_mod: distributed variant — per-column coarse ids (GLOBAL)
+                         ncols_mod=None, generator=None, structure=None):
+    """structure: the aggregate-membership CSR (offsets, fine ids) of
+    aggregate_csr when the caller holds it already; built here otherwise.
+
+    agg_col/ncols_mod: distributed variant — per-column coarse ids (GLOBAL)
     and the global coarse column count; defaults to the single-process case.
 
     Real and complex values alike (complex: scalar matrices only). A
@@ -544,14 +578,10 @@ def galerkin_aggregation(A, aggregates, num_aggregates, agg_col=None,
             "complex modes (dZZI / dCCI / dZCI)")
     if A.block_dim == 1 and generator != "THRUST":
         # aggregate-membership CSR: coarse row -> fine member rows
-        agg64 = aggregates.to(torch.int64)
-        counts = torch.bincount(agg64, minlength=num_aggregates)
-        m_ro = torch.zeros(num_aggregates + 1, dtype=torch.int64,
-                           device=A.device)
-        m_ro[1:] = torch.cumsum(counts, 0)
-        fids = torch.argsort(agg64, stable=True).to(torch.int32)
+        m_ro, fids = structure if structure is not None \
+            else aggregate_csr(aggregates, num_aggregates)
         ro, ci, va, big = _core.spgemm_hash(
-            m_ro.to(torch.int32), fids, A.values,   # vaA unused in mode 1
+            m_ro, fids, A.values,   # vaA unused in mode 1
             A.row_offsets, A.col_indices, A.values,
             agg_col, 1, max(A.nnz, 1),
             64 if A.nnz <= 48 * max(num_aggregates, 1) else 512)
@@ -787,7 +817,7 @@ def ilu0_solve(A, factors, coloring, r, x, relaxation=1.0):
     # color-sorted slabs (same layout win as the DILU sweeps)
     lu_s, diag_s = _slab_copy(
         st, "ilu", factors, lambda f: (
-            f.reshape(-1)[st.nzmap],
+            _gather_nz(f, st.nzmap),
             f.reshape(-1)[_didx(A).to(torch.int64)][st.perm]))
     _core.ilu0_apply_sorted(st.ro_s, st.ci_s, lu_s, diag_s, st.slot_of_row,
                             coloring.rows_sorted, coloring.bounds,

@@ -11,6 +11,7 @@ human table to stderr.
     python bench_kernels.py [--size 192] [--iters 20] [--section dilu_lanes]
     python bench_kernels.py --size 64 --iters 50 --section dilu_small
     python bench_kernels.py [--size 192] [--iters 20] [--section dilu_stream]
+    python bench_kernels.py [--size 192] [--iters 5] [--section setup]
 """
 
 import argparse
@@ -300,19 +301,109 @@ def bench_dilu_small(A, iters, sync, rec, max_rows=32768):
         A = ops.galerkin_aggregation(A, agg.to(A.row_offsets.device), num)
 
 
+def bench_setup(A, iters, sync, rec):
+    """The setup pieces outside the sparse products, on the 7-point matrix
+    and on its first two Galerkin levels under SIZE_2 aggregation: the
+    coloring loop, the matching loop with its renumbering, the color order
+    (MatrixColoring), the aggregate-membership CSR and the slab structure.
+    The two round loops also run cut off after their first round, next to
+    the bytes that round has to move; that figure carries the loop's fixed
+    cost (two allocations, one fill, one read-back). Where the tree has the
+    batch argument, the loops are timed for k = 1, 2, 4, 8 rounds per
+    read-back next to the default rule, and the matching with its edge
+    weights computed in every round and once per call. A tree without the native entries
+    times the torch expressions it runs in their place, so the same section
+    compares two trees piece by piece."""
+    from amgx_amd import _core, ops
+    from amgx_amd.amg.coloring import MatrixColoring
+    from amgx_amd.ops import gpu as G
+
+    batched = hasattr(G, "ROUND_BATCH")
+
+    def first_round_color():
+        try:
+            _core.color_minmax(A.row_offsets, A.col_indices, A.n_rows, 1, 0, 0)
+        except RuntimeError:
+            pass    # one round does not color the graph: that is the point
+
+    def torch_aggregate_csr(agg, num):
+        a64 = agg.to(torch.int64)
+        order = torch.argsort(a64, stable=True).to(torch.int32)
+        off = torch.zeros(num + 1, dtype=torch.int64, device=agg.device)
+        torch.cumsum(torch.bincount(a64, minlength=num), 0, out=off[1:])
+        return off.to(torch.int32), order
+
+    def slabs(col):
+        A._cache.pop("slabs", None)
+        return G._slabs(A, col)
+
+    for level in range(3):
+        if level:
+            A = ops.galerkin_aggregation(A, agg, num)
+        n, nnz = A.n_rows, A.nnz
+        tag = f"L{level}"
+        print(f"{tag}: {n} rows, {nnz / max(n, 1):.1f} entries/row",
+              file=sys.stderr)
+        colors, nc = ops.color_matrix(A)
+        agg, num = ops.size2_matching(A)
+        G._tidx(A)   # cached by the matrix: not part of the matching loop
+        rec(f"setup_color_minmax_{tag}",
+            bench(lambda: ops.color_matrix(A), iters, sync), rows=n,
+            colors=nc)
+        rec(f"setup_color_round1_{tag}", bench(first_round_color, iters, sync),
+            nnz * 4 + n * 12, rows=n)
+        rec(f"setup_size2_match_renumber_{tag}",
+            bench(lambda: ops.size2_matching(A), iters, sync), rows=n,
+            aggregates=num)
+        rec(f"setup_size2_round1_{tag}",
+            bench(lambda: ops.size2_matching(A, max_iterations=1), iters,
+                  sync),
+            # propose (structure, values, transpose index, diagonal, state),
+            # match (proposals read and gathered), singleton sweep, renumber
+            nnz * 16 + n * 24 + n * 12 + nnz * 16 + n * 20 + n * 16, rows=n)
+        if batched:
+            for k in (1, 2, 4, 8):
+                rec(f"setup_color_minmax_{tag}_k{k}",
+                    bench(lambda: G.color_matrix(A, batch=k), iters, sync))
+                rec(f"setup_size2_match_renumber_{tag}_k{k}",
+                    bench(lambda: G.size2_matching(A, batch=k), iters, sync))
+            # propose-kernel A/B: weights computed in every round (w0)
+            # against once per call into one double per entry (w1)
+            for w in (0, 1):
+                rec(f"setup_size2_roots_{tag}_w{w}",
+                    bench(lambda: G.size2_roots(A, weights=bool(w)), iters,
+                          sync))
+        rec(f"setup_color_order_{tag}",
+            bench(lambda: MatrixColoring(colors, nc), iters, sync), rows=n)
+        build_csr = (lambda: G.aggregate_csr(agg, num)) \
+            if hasattr(G, "aggregate_csr") \
+            else (lambda: torch_aggregate_csr(agg, num))
+        rec(f"setup_aggregate_csr_{tag}", bench(build_csr, iters, sync),
+            rows=n)
+        col = MatrixColoring(colors, nc)
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        rec(f"setup_slabs_{tag}", bench(lambda: slabs(col), iters, sync),
+            rows=n,
+            peak_extra_MB=(torch.cuda.max_memory_allocated() - base) / 1e6)
+        A._cache.pop("slabs", None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=192)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--section", default="all",
                     choices=("all", "multi_pairwise", "dilu_lanes",
-                             "dilu_small", "dilu_stream"),
+                             "dilu_small", "dilu_stream", "setup"),
                     help="multi_pairwise: only the MULTI_PAIRWISE records; "
                          "dilu_lanes: the DILU sweeps by lanes per row; "
                          "dilu_small: the one-launch DILU apply against the "
                          "per-color sweeps on the small Galerkin levels; "
                          "dilu_stream: the stream form of the DILU sweeps "
-                         "against the lane forms")
+                         "against the lane forms; setup: the coloring and "
+                         "matching loops and the orderings of the setup "
+                         "path, per piece")
     args = ap.parse_args()
     sys.path.insert(0, ".")
     from amgx_amd import ops
@@ -355,6 +446,11 @@ def main():
         if dev == "cpu":
             sys.exit("--section dilu_stream times device kernels: no GPU")
         bench_dilu_stream(A, args.iters, sync, rec)
+        return
+    if args.section == "setup":
+        if dev == "cpu":
+            sys.exit("--section setup times device kernels: no GPU")
+        bench_setup(A, args.iters, sync, rec)
         return
     if args.section == "dilu_small":
         if dev == "cpu":

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         os.path.join(csrc, "bindings.cpp"),
         os.path.join(csrc, "kernels_solve.hip"),
         os.path.join(csrc, "kernels_setup.hip"),
+        os.path.join(csrc, "kernels_order.hip"),
         os.path.join(csrc, "kernels_classical.hip"),
         os.path.join(csrc, "kernels_mfma.hip"),
         os.path.join(csrc, "kernels_spgemm.hip"),
