@@ -598,6 +598,58 @@ bool dilu_stream(double entries_per_row, int64_t color_rows, bool split) {
     return entries_per_row > 0.0 && color_rows >= least;
 }
 
+// What dilu_split and dilu_small ask of their common arguments (`fn` names
+// the caller in the messages), and the lanes of the two slabs: a forced
+// `lanes`, or dilu_lanes of the slab's entries per row (the entry counts are
+// the tensors' sizes, no read-back; the forward slab of a plain apply and U
+// are split parts). y is looked at when fused and present.
+struct DiluSlabs {
+    double epr_f, epr_u;   // entries per row of the forward / backward slab
+    int lanes_f, lanes_u;
+};
+static DiluSlabs dilu_check_args(const char* fn, const Tensor& ro_f,
+                                 const Tensor& ci_f, const Tensor& va_f,
+                                 const Tensor& ro_u, const Tensor& ci_u,
+                                 const Tensor& va_u, const Tensor& einv_s,
+                                 const Tensor& rows_sorted,
+                                 const std::vector<int64_t>& bounds,
+                                 const Tensor& rhs, const Tensor& w,
+                                 const Tensor& x, bool fused, int64_t lanes,
+                                 const c10::optional<Tensor>& y_opt) {
+    int64_t n = (int64_t)ro_u.numel() - 1;
+    TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
+                    einv_s.numel() == n,
+                fn, ": slabs, rows_sorted and Einv disagree on n");
+    TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n,
+                fn, ": color bounds do not cover the n rows");
+    TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
+                fn, ": scalar slabs hold one value per column index");
+    TORCH_CHECK(rhs.numel() >= n && x.numel() >= n && w.numel() >= n &&
+                    (!fused || w.numel() >= x.numel()),
+                fn, ": vectors shorter than the matrix");
+    TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
+                    rhs.scalar_type() == x.scalar_type() &&
+                    va_u.scalar_type() == va_f.scalar_type() &&
+                    einv_s.scalar_type() == va_f.scalar_type(),
+                fn, ": mixed value types");
+    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
+                fn, ": lanes must be 0 (routed), 1 or 8");
+    if (fused && y_opt.has_value()) {
+        const Tensor& y = *y_opt;
+        TORCH_CHECK(y.is_contiguous() && y.device() == x.device() &&
+                        y.scalar_type() == x.scalar_type() &&
+                        y.numel() >= x.numel(),
+                    fn, ": y must be a vector like w");
+    }
+    double rows = (double)std::max<int64_t>(n, 1);
+    DiluSlabs r;
+    r.epr_f = (double)ci_f.numel() / rows;
+    r.epr_u = (double)ci_u.numel() / rows;
+    r.lanes_f = lanes ? (int)lanes : (int)dilu_lanes(r.epr_f, !fused);
+    r.lanes_u = lanes ? (int)lanes : (int)dilu_lanes(r.epr_u, true);
+    return r;
+}
+
 // per-color scalar DILU apply x += relax * M^{-1} rhs over the strict
 // color-split slabs; w is the scratch vector (column-extended).
 // fused: rhs is b, the forward sweep reads the full slab (ro_f, ci_f, va_f)
@@ -607,10 +659,8 @@ bool dilu_stream(double entries_per_row, int64_t color_rows, bool split) {
 // forward sweep reads the L slab (same three arguments). Neither scratch
 // vector needs zeroing. The backward sweep runs in place in w over the U slab
 // and updates x as it goes. No host sync: capturable in a hipGraph.
-// lanes: 0 routes each slab by its entries per row (dilu_lanes; the entry
-// counts are the tensors' sizes, no read-back; the forward slab of a plain
-// apply and U are split parts), 1 or 8 forces that form for both sweeps
-// (tests and bench_kernels.py).
+// lanes: 0 routes each slab by its entries per row (dilu_check_args), 1 or 8
+// forces that form for both sweeps (tests and bench_kernels.py).
 // form: 0 routes each color of each slab between its lane form and the
 // stream form (dilu_stream; a forced lanes keeps the lane forms), 1 keeps
 // the lane forms, 2 takes the stream form for every color and goes with
@@ -620,44 +670,17 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                 std::vector<int64_t> bounds, Tensor rhs, Tensor w, Tensor x,
                 double relax, bool fused, int64_t lanes,
                 c10::optional<Tensor> y_opt, int64_t form) {
-    int64_t n = (int64_t)ro_u.numel() - 1;
-    TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
-                    einv_s.numel() == n,
-                "dilu_split: slabs, rows_sorted and Einv disagree on n");
     TORCH_CHECK(form == 0 || form == 1 || form == 2,
                 "dilu_split: form must be 0 (routed), 1 (lane forms) or 2 "
                 "(stream form)");
     TORCH_CHECK(form != 2 || lanes == 0,
                 "dilu_split: the stream form takes no lanes");
-    TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n,
-                "dilu_split: color bounds do not cover the n rows");
-    TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
-                "dilu_split: scalar slabs hold one value per column index");
-    TORCH_CHECK(rhs.numel() >= n && x.numel() >= n && w.numel() >= n &&
-                    (!fused || w.numel() >= x.numel()),
-                "dilu_split: vectors shorter than the matrix");
-    TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-                    rhs.scalar_type() == x.scalar_type() &&
-                    va_u.scalar_type() == va_f.scalar_type() &&
-                    einv_s.scalar_type() == va_f.scalar_type(),
-                "dilu_split: mixed value types");
-    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
-                "dilu_split: lanes must be 0 (routed), 1 or 8");
-    Tensor y;
-    if (fused) {
-        y = y_opt.has_value() ? *y_opt : torch::empty_like(w);
-        TORCH_CHECK(y.is_contiguous() && y.device() == x.device() &&
-                        y.scalar_type() == x.scalar_type() &&
-                        y.numel() >= x.numel(),
-                    "dilu_split: y must be a vector like w");
-    }
-    double rows = (double)std::max<int64_t>(n, 1);
-    int lanes_f = lanes ? (int)lanes
-                        : (int)dilu_lanes((double)ci_f.numel() / rows, !fused);
-    int lanes_u = lanes ? (int)lanes
-                        : (int)dilu_lanes((double)ci_u.numel() / rows, true);
-    const double epr_f = (double)ci_f.numel() / rows;
-    const double epr_u = (double)ci_u.numel() / rows;
+    if (fused && !y_opt.has_value()) y_opt = torch::empty_like(w);
+    const DiluSlabs sl =
+        dilu_check_args("dilu_split", ro_f, ci_f, va_f, ro_u, ci_u, va_u,
+                        einv_s, rows_sorted, bounds, rhs, w, x, fused, lanes,
+                        y_opt);
+    Tensor y = fused ? *y_opt : Tensor();
     auto pick = [&](int lane_form, double epr, int64_t count, bool split) {
         bool stream = form == 2 || (form == 0 && lanes == 0 &&
                                     dilu_stream(epr, count, split));
@@ -676,20 +699,20 @@ void dilu_split(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                     (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(x),
                     dptr<scalar_v>(w), dptr<scalar_v>(y),
-                    pick(lanes_f, epr_f, e - s, false), st);
+                    pick(sl.lanes_f, sl.epr_f, e - s, false), st);
             else
                 amgx_hip::dilu_fwd_lower<scalar_a, scalar_v>(
                     iptr(ro_f) + s, iptr(ci_f), dptr<scalar_a>(va_f),
                     dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                     (int)(e - s), dptr<scalar_v>(rhs), dptr<scalar_v>(w),
-                    pick(lanes_f, epr_f, e - s, true), st);
+                    pick(sl.lanes_f, sl.epr_f, e - s, true), st);
         });
         for_each_color(bounds, false, [&](int, int64_t s, int64_t e) {
             amgx_hip::dilu_bwd_upper<scalar_a, scalar_v>(
                 iptr(ro_u) + s, iptr(ci_u), dptr<scalar_a>(va_u),
                 dptr<scalar_a>(einv_s) + s, iptr(rows_sorted) + s,
                 (int)(e - s), dptr<scalar_v>(w), dptr<scalar_v>(x),
-                (scalar_v)relax, pick(lanes_u, epr_u, e - s, true), st);
+                (scalar_v)relax, pick(sl.lanes_u, sl.epr_u, e - s, true), st);
         });
     });
 }
@@ -711,52 +734,28 @@ void dilu_small(Tensor ro_f, Tensor ci_f, Tensor va_f, Tensor ro_u,
     TORCH_CHECK(any_size || n <= amgx_hip::DILU_SMALL_ROWS,
                 "dilu_small: scalar levels of more than ",
                 amgx_hip::DILU_SMALL_ROWS, " rows run dilu_split");
-    TORCH_CHECK(ro_f.numel() == n + 1 && rows_sorted.numel() == n &&
-                    einv_s.numel() == n,
-                "dilu_small: slabs, rows_sorted and Einv disagree on n");
-    TORCH_CHECK(!bounds.empty() && bounds.front() == 0 && bounds.back() == n &&
-                    bounds_dev.numel() == nc + 1 &&
+    const DiluSlabs sl =
+        dilu_check_args("dilu_small", ro_f, ci_f, va_f, ro_u, ci_u, va_u,
+                        einv_s, rows_sorted, bounds, rhs, w, x, fused, lanes,
+                        y_opt);
+    TORCH_CHECK(bounds_dev.numel() == nc + 1 &&
                     bounds_dev.scalar_type() == torch::kInt32,
                 "dilu_small: color bounds do not cover the n rows");
-    TORCH_CHECK(va_f.numel() == ci_f.numel() && va_u.numel() == ci_u.numel(),
-                "dilu_small: scalar slabs hold one value per column index");
-    TORCH_CHECK(rhs.numel() >= n && x.numel() >= n && w.numel() >= n &&
-                    (!fused || w.numel() >= x.numel()),
-                "dilu_small: vectors shorter than the matrix");
-    TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-                    rhs.scalar_type() == x.scalar_type() &&
-                    va_u.scalar_type() == va_f.scalar_type() &&
-                    einv_s.scalar_type() == va_f.scalar_type(),
-                "dilu_small: mixed value types");
-    TORCH_CHECK(lanes == 0 || lanes == 1 || lanes == 8,
-                "dilu_small: lanes must be 0 (routed), 1 or 8");
     TORCH_CHECK(sweeps >= 1 && sweeps <= (1 << 20),
                 "dilu_small: sweeps must be at least 1");
     for (Tensor t : {ro_f, ci_f, va_f, ro_u, ci_u, va_u, einv_s, rows_sorted,
                      bounds_dev, rhs, w, x})
         check_dev(t);
-    Tensor y;
-    if (fused) {
-        TORCH_CHECK(y_opt.has_value(), "dilu_small: a fused apply needs y");
-        y = *y_opt;
-        TORCH_CHECK(y.is_contiguous() && y.device() == x.device() &&
-                        y.scalar_type() == x.scalar_type() &&
-                        y.numel() >= x.numel(),
-                    "dilu_small: y must be a vector like w");
-    }
-    double rows = (double)std::max<int64_t>(n, 1);
-    int lanes_f = lanes ? (int)lanes
-                        : (int)dilu_lanes((double)ci_f.numel() / rows, !fused);
-    int lanes_u = lanes ? (int)lanes
-                        : (int)dilu_lanes((double)ci_u.numel() / rows, true);
+    TORCH_CHECK(!fused || y_opt.has_value(),
+                "dilu_small: a fused apply needs y");
     DISPATCH(AMGX_VALUE_PAIRS, "dilu_small", (va_f, x), [&] {
         amgx_hip::dilu_small<scalar_a, scalar_v>(
             iptr(ro_f), iptr(ci_f), dptr<scalar_a>(va_f), iptr(ro_u),
             iptr(ci_u), dptr<scalar_a>(va_u), dptr<scalar_a>(einv_s),
             iptr(rows_sorted), iptr(bounds_dev), (int)nc, dptr<scalar_v>(rhs),
-            dptr<scalar_v>(w), fused ? dptr<scalar_v>(y) : nullptr,
+            dptr<scalar_v>(w), fused ? dptr<scalar_v>(*y_opt) : nullptr,
             dptr<scalar_v>(x), (scalar_v)relax, (long long)x.numel(), fused,
-            lanes_f, lanes_u, (int)sweeps, cur_stream());
+            sl.lanes_f, sl.lanes_u, (int)sweeps, cur_stream());
     });
 }
 

@@ -138,12 +138,11 @@ void gs_rows_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
 // forward sweep folds the residual in, so M^{-1}(b - A x) costs one matrix
 // read less; scalar and block-4 only.
 // `sweeps` whole applies for a small scalar level in one single-workgroup
-// launch, with the arithmetic (and bits) of the per-color kernels below:
-// fused sweeps the full slab (ro_f, ci_f, va_f) gathering y = x + w, with
-// y = x + 0 over vec_n entries written by the kernel at each apply; plain
-// sweeps the L slab (same arguments, y unused) gathering w; backward over U in
-// place in w with x += relax z folded in. w and y need no zeroing. lanes_f /
-// lanes_u: 1 or 8 lanes per row of the forward / backward slab.
+// launch, with the row rules (and bits) of the per-color sweeps below: fused
+// sweeps the full slab (ro_f, ci_f, va_f), with y = x + 0 over vec_n entries
+// written by the kernel at each apply; plain sweeps the L slab (same
+// arguments, y unused); backward over U. lanes_f / lanes_u: 1 or 8 lanes per
+// row of the forward / backward slab.
 // Levels of at most DILU_SMALL_ROWS rows take it; the boundary is the
 // measured crossover with the per-color path, whose three sweeps cost about
 // the same 0.3 ms of launches from 1400 to 27000 rows while one workgroup's
@@ -176,18 +175,18 @@ template <typename TA, typename TV>
 void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
                      const TA* einv_s, const int* rows, int count,
                      const TV* wv, TV* z, int b, hipStream_t s);
-// Scalar per-color sweeps, with lanes = 1 or 8 lanes per row (same bits);
-// ro_* / rows / einv_s pre-offset to the color base.
-// Fused forward over the full slab: dilu_y_init writes y = x + 0 over the
-// column-extended length once per apply, then per color
-// w_i = Einv_i (rhs_i - sum a_ij y_j), y_i = x_i + w_i; neither w nor y needs
-// zeroing. Over the strict color-split slabs (slab_split_*): plain forward
-// w_i = Einv_i (rhs_i - sum_L a_ij w_j), no pre-zeroed w; backward in place
-// z_i = w_i - Einv_i sum_U a_ij w_j stored to w[i], with x[i] += relax * z_i
-// folded in.
-// lanes = DILU_STREAM selects the stream form of the same three sweeps (same
-// bits again): a wave takes DILU_STREAM_ROWS consecutive rows of the color,
-// one lane per row, and streams their contiguous entries through a
+// Scalar per-color sweeps; ro_* / rows / einv_s pre-offset to the color base.
+// Each is one row rule; neither w nor y needs zeroing.
+//   dilu_fwd_full, over the full slab: w_i = Einv_i (rhs_i - sum a_ij y_j),
+//     y_i = x_i + w_i, after dilu_y_init has written y = x + 0 over the
+//     column-extended length once per apply.
+//   dilu_fwd_lower, over the strict color-split L slab (slab_split_*):
+//     w_i = Einv_i (rhs_i - sum_L a_ij w_j).
+//   dilu_bwd_upper, over the U slab, in place: z_i = w_i - Einv_i sum_U
+//     a_ij w_j stored to w[i], with x[i] += relax * z_i folded in.
+// lanes = 1 or 8 lanes per row; lanes = DILU_STREAM selects the stream form
+// (all the same bits): a wave takes DILU_STREAM_ROWS consecutive rows of the
+// color, one lane per row, and streams their contiguous entries through a
 // wave-private LDS window of DILU_STREAM_WINDOW_BYTES bytes, which holds
 // dilu_stream_window_of(bytes of one value and one gathered vector entry)
 // entries: 512 in fp64 and with an fp32 matrix, 256 in complex128.

@@ -915,19 +915,14 @@ void dilu_setup_color(const int* ro, const int* ci, const T* va,
 // local columns, U those of later colors, both in slab order, so the sums
 // below run in the order of a full-row product with the zero terms left out.
 //
-// The three scalar kernels take LANES lanes per row (slab_row_dot_lanes): one
-// where rows are short, 8 where they are long (the Galerkin levels); lane 0
-// does the row's own reads and writes, and both forms give the same bits.
-//
-// fused forward (full slab): w_i = Einv_i (b_i - sum_k a_k y_k) with the one
-// gathered vector y = x + w kept next to w: dilu_y_init writes y = x + 0 (the
-// value x_k + w_k had under a zeroed w, sign of zero included) and each row
-// stores y_i = x_i + w_i with its w_i, the sum rounded on its own as the
-// gathered x[j] + w[j] was. The product so only picks up earlier colors
-// (valid coloring => no same-color off-diagonals; the diagonal meets y_i =
-// x_i). It replaces residual kernel + sweep with one matrix read,
-// mathematically identical to r = b - A x; M w = r; nothing reads a w or y
-// that this apply has not written.
+// A scalar sweep is a row rule (DiluFwdFull, DiluFwdLower, DiluBwdUpper)
+// run by a launch shape (dilu_lane_kernel, dilu_stream_kernel,
+// dilu_small_kernel). The rule says what a row does around its product: the
+// vector gathered(), the row's own reads read(t, i) of slab slot t and row
+// i = rows[t], and the epilogue finish(i, own, sum) with its stores. The
+// shape says which lanes compute the product and when the own reads are
+// issued. Every rule gives the same bits under every shape
+// (tests/test_gpu_dilu_{lanes,small,stream}.py).
 template <typename T>
 __device__ __forceinline__ T add_unfused(T a, T b) {
 #pragma clang fp contract(off)
@@ -947,75 +942,17 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_y_init_kernel(
     if (j < n) y[j] = x[j] + TV(0);
 }
 
-template <int LANES, typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_full(
-    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
-    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
-    const TV* __restrict__ x, TV* __restrict__ w, TV* y) {
-    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g / LANES >= count) return;   // uniform over the lanes of a row
-    int t = (int)(g / LANES);
-    int lane = threadIdx.x & (LANES - 1);
-    TV sum = slab_row_dot_lanes<LANES>(ro_s, ci_s, va_s, t, lane, y);
-    if (lane != 0) return;
-    int i = rows[t];
-    TV wi = (TV)einv_s[t] * (rhs[i] - sum);
-    w[i] = wi;
-    y[i] = add_unfused(x[i], wi);
-}
-
-// plain forward over L: w_i = Einv_i (rhs_i - sum_L A_ij w_j).  Only rows of
-// earlier colors, already written by this sweep, are read: w needs no
-// zeroing.
-template <int LANES, typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_scalar_lower(
-    const int* __restrict__ ro_l, const int* __restrict__ ci_l,
-    const TA* __restrict__ va_l, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
-    TV* w) {
-    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g / LANES >= count) return;
-    int t = (int)(g / LANES);
-    int lane = threadIdx.x & (LANES - 1);
-    TV sum = slab_row_dot_lanes<LANES>(ro_l, ci_l, va_l, t, lane, w);
-    if (lane != 0) return;
-    int i = rows[t];
-    w[i] = (TV)einv_s[t] * (rhs[i] - sum);
-}
-
-// backward over U, in place, colors descending: z_i = w_i - Einv_i sum_U
-// A_ij z_j.  Later colors already hold z in w, this color still holds w, so
-// z_i overwrites w_i; the relaxed update x_i += relax z_i (the axpy
-// expression) rides along since the sweep never reads x.  The last color's
-// U rows are empty: its launch reads ro_u, w and x only.
-template <int LANES, typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_scalar_upper(
-    const int* __restrict__ ro_u, const int* __restrict__ ci_u,
-    const TA* __restrict__ va_u, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, TV* w, TV* __restrict__ x,
-    TV relax) {
-    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g / LANES >= count) return;
-    int t = (int)(g / LANES);
-    int lane = threadIdx.x & (LANES - 1);
-    TV sum = slab_row_dot_lanes<LANES>(ro_u, ci_u, va_u, t, lane, w);
-    if (lane != 0) return;
-    int i = rows[t];
-    TV z = w[i] - (TV)einv_s[t] * sum;
-    w[i] = z;
-    x[i] += relax * z;
-}
-
-// The products of a row's epilogue in the stream kernels. In a complex product
-// a * o the compiler contracts the imaginary part a.re * o.im + a.im * o.re
-// to one rounded product and one fused multiply-add, and which of the two
-// products it rounds depends on the code around the expression: in the lane
-// forms Einv_i (b_i - sum) and relax * z round a.re * o.im, Einv_i * sum of
-// the backward kernel rounds a.im * o.re (read off their ISA;
-// tests/test_gpu_dilu_stream.py compares the bits). The stream kernels spell
-// the choice out, so they give the lane forms' bits whatever surrounds the
-// call. A real product is a real product.
+// The products of a row's epilogue, in the two spellings the shapes use. In a
+// complex product a * o the compiler contracts the imaginary part
+// a.re * o.im + a.im * o.re to one rounded product and one fused
+// multiply-add, and which of the two products it rounds depends on the code
+// around the expression: in the lane and one-launch shapes, which take the
+// plain e * s (PINNED = false), Einv_i (b_i - sum) and relax * z round
+// a.re * o.im, Einv_i * sum of the backward rule rounds a.im * o.re (read
+// off their ISA; tests/test_gpu_dilu_stream.py compares the bits). The stream
+// shape spells that choice out (PINNED = true, ROUND_RE_IM as just listed), so
+// it gives the same bits whatever surrounds the call. A real product is a
+// real product.
 __device__ __forceinline__ double fma_of(double a, double b, double c) {
     return __builtin_fma(a, b, c);
 }
@@ -1035,83 +972,134 @@ __device__ __forceinline__ cplx<R> times_pinned(const cplx<R>& e,
                        : fma_of(e.re, s.im, e.im * s.re);
     return cplx<R>(re, im);
 }
+template <bool PINNED, bool ROUND_RE_IM, typename T>
+__device__ __forceinline__ T row_times(const T& e, const T& s) {
+    if constexpr (PINNED) return times_pinned<ROUND_RE_IM>(e, s);
+    else return e * s;
+}
 
-// Stream forms of the three kernels above (slab_row_dot_stream): a block of
-// DILU_STREAM_WAVES waves, 64 rows of the color per wave, one LDS region per
-// wave. The row's own reads are issued ahead of the windows, so they overlap
-// the slab loads; the stores are those of the lane forms. A wave past the
-// color's end leaves as a whole, before any window; in the color's last wave
-// a lane without a row reads as the color's last row (tc) and stores nothing.
+// fused forward (full slab): w_i = Einv_i (b_i - sum_k a_k y_k) with the one
+// gathered vector y = x + w kept next to w: dilu_y_init writes y = x + 0 (the
+// value x_k + w_k had under a zeroed w, sign of zero included) and each row
+// stores y_i = x_i + w_i with its w_i, the sum rounded on its own as the
+// gathered x[j] + w[j] was. The product so only picks up earlier colors
+// (valid coloring => no same-color off-diagonals; the diagonal meets y_i =
+// x_i). It replaces residual kernel + sweep with one matrix read,
+// mathematically identical to r = b - A x; M w = r; nothing reads a w or y
+// that this apply has not written.
+template <typename TA, typename TV>
+struct DiluFwdFull {
+    const TA* einv_s;
+    const TV* rhs;
+    const TV* x;
+    TV* w;
+    TV* y;
+    struct Own { TA e; TV r, x; };
+    __device__ const TV* gathered() const { return y; }
+    __device__ Own read(int t, int i) const {
+        return {einv_s[t], rhs[i], x[i]};
+    }
+    template <bool PINNED>
+    __device__ void finish(int i, const Own& o, TV sum) const {
+        TV wi = row_times<PINNED, true>((TV)o.e, o.r - sum);
+        w[i] = wi;
+        y[i] = add_unfused(o.x, wi);
+    }
+};
+
+// plain forward over L: w_i = Einv_i (rhs_i - sum_L A_ij w_j).  Only rows of
+// earlier colors, already written by this sweep, are read: w needs no
+// zeroing.
+template <typename TA, typename TV>
+struct DiluFwdLower {
+    const TA* einv_s;
+    const TV* rhs;
+    TV* w;
+    struct Own { TA e; TV r; };
+    __device__ const TV* gathered() const { return w; }
+    __device__ Own read(int t, int i) const { return {einv_s[t], rhs[i]}; }
+    template <bool PINNED>
+    __device__ void finish(int i, const Own& o, TV sum) const {
+        w[i] = row_times<PINNED, true>((TV)o.e, o.r - sum);
+    }
+};
+
+// backward over U, in place, colors descending: z_i = w_i - Einv_i sum_U
+// A_ij z_j.  Later colors already hold z in w, this color still holds w (so
+// w_i may be read ahead of the product), and z_i overwrites w_i; the relaxed
+// update x_i += relax z_i (the axpy expression) rides along since the sweep
+// never reads x.  The last color's U rows are empty: its launch reads ro_u,
+// w and x only.
+template <typename TA, typename TV>
+struct DiluBwdUpper {
+    const TA* einv_s;
+    TV* w;
+    TV* x;
+    TV relax;
+    struct Own { TA e; TV w, x; };
+    __device__ const TV* gathered() const { return w; }
+    __device__ Own read(int t, int i) const { return {einv_s[t], w[i], x[i]}; }
+    template <bool PINNED>
+    __device__ void finish(int i, const Own& o, TV sum) const {
+        TV z = o.w - row_times<PINNED, false>((TV)o.e, sum);
+        w[i] = z;
+        x[i] = o.x + row_times<PINNED, true>(relax, z);
+    }
+};
+
+// Lane shape: LANES lanes per row (slab_row_dot_lanes), one where rows are
+// short, 8 where they are long (the Galerkin levels); lane 0 does the row's
+// own reads, after the product, and its stores.
+template <int LANES, typename TA, typename TV, typename Rule>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_lane_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const TA* __restrict__ va, const int* __restrict__ rows, int count,
+    Rule rule) {
+    long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g / LANES >= count) return;   // uniform over the lanes of a row
+    int t = (int)(g / LANES);
+    int lane = threadIdx.x & (LANES - 1);
+    TV sum = slab_row_dot_lanes<LANES>(ro, ci, va, t, lane, rule.gathered());
+    if (lane != 0) return;
+    int i = rows[t];
+    rule.template finish<false>(i, rule.read(t, i), sum);
+}
+
+// Stream shape (slab_row_dot_stream): a block of DILU_STREAM_WAVES waves, 64
+// rows of the color per wave, one LDS region per wave. The row's own reads
+// are issued ahead of the windows, so they overlap the slab loads. A wave
+// past the color's end leaves as a whole, before any window; in the color's
+// last wave a lane without a row reads as the color's last row (tc) and
+// stores nothing.
 constexpr int DILU_STREAM_WAVES = AMGX_BLOCK / 64;
 static inline int dilu_stream_grid(int count) {
     const int per_block = DILU_STREAM_WAVES * DILU_STREAM_ROWS;
     return (count + per_block - 1) / per_block;
 }
-#define DILU_STREAM_PROLOGUE(RO)                                               \
-    __shared__ __attribute__((aligned(16))) char                               \
-        lds[DILU_STREAM_WAVES * DILU_STREAM_WINDOW_BYTES];                     \
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;                \
-    const long long t0l =                                                      \
-        ((long long)blockIdx.x * DILU_STREAM_WAVES + wave) * DILU_STREAM_ROWS; \
-    if (t0l >= count) return;                                                  \
-    const int t0 = (int)t0l;                                                   \
-    const bool has_row = t0 + lane < count;                                    \
-    const int tc = has_row ? t0 + lane : count - 1;                            \
-    int rs = RO[tc], re = RO[tc + 1];                                          \
-    const int i = rows[tc];                                                    \
-    const TA ei = einv_s[tc];                                                  \
-    if (!has_row) rs = re = 0;                                                 \
-    char* region = lds + wave * DILU_STREAM_WINDOW_BYTES
-
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_stream_full(
-    const int* __restrict__ ro_s, const int* __restrict__ ci_s,
-    const TA* __restrict__ va_s, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
-    const TV* __restrict__ x, TV* __restrict__ w, TV* y) {
-    DILU_STREAM_PROLOGUE(ro_s);
-    const TV ri = rhs[i], xi = x[i];
-    TV sum = slab_row_dot_stream(ci_s, va_s, t0, count, lane, rs, re, y,
-                                 region);
+template <typename TA, typename TV, typename Rule>
+__global__ __launch_bounds__(AMGX_BLOCK) void dilu_stream_kernel(
+    const int* __restrict__ ro, const int* __restrict__ ci,
+    const TA* __restrict__ va, const int* __restrict__ rows, int count,
+    Rule rule) {
+    __shared__ __attribute__((aligned(16))) char
+        lds[DILU_STREAM_WAVES * DILU_STREAM_WINDOW_BYTES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long t0l =
+        ((long long)blockIdx.x * DILU_STREAM_WAVES + wave) * DILU_STREAM_ROWS;
+    if (t0l >= count) return;
+    const int t0 = (int)t0l;
+    const bool has_row = t0 + lane < count;
+    const int tc = has_row ? t0 + lane : count - 1;
+    int rs = ro[tc], re = ro[tc + 1];
+    const int i = rows[tc];
+    const auto own = rule.read(tc, i);
+    if (!has_row) rs = re = 0;
+    TV sum = slab_row_dot_stream(ci, va, t0, count, lane, rs, re,
+                                 rule.gathered(),
+                                 lds + wave * DILU_STREAM_WINDOW_BYTES);
     if (!has_row) return;
-    TV wi = times_pinned<true>((TV)ei, ri - sum);
-    w[i] = wi;
-    y[i] = add_unfused(xi, wi);
+    rule.template finish<true>(i, own, sum);
 }
-
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_fwd_stream_lower(
-    const int* __restrict__ ro_l, const int* __restrict__ ci_l,
-    const TA* __restrict__ va_l, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, const TV* __restrict__ rhs,
-    TV* w) {
-    DILU_STREAM_PROLOGUE(ro_l);
-    const TV ri = rhs[i];
-    TV sum = slab_row_dot_stream(ci_l, va_l, t0, count, lane, rs, re, w,
-                                 region);
-    if (!has_row) return;
-    w[i] = times_pinned<true>((TV)ei, ri - sum);
-}
-
-// w[i] is this color's own, still the forward w: read ahead of the windows
-template <typename TA, typename TV>
-__global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_stream_upper(
-    const int* __restrict__ ro_u, const int* __restrict__ ci_u,
-    const TA* __restrict__ va_u, const TA* __restrict__ einv_s,
-    const int* __restrict__ rows, int count, TV* w, TV* __restrict__ x,
-    TV relax) {
-    DILU_STREAM_PROLOGUE(ro_u);
-    const TV wi = w[i];
-    TV xi = x[i];
-    TV sum = slab_row_dot_stream(ci_u, va_u, t0, count, lane, rs, re, w,
-                                 region);
-    if (!has_row) return;
-    TV z = wi - times_pinned<false>((TV)ei, sum);
-    w[i] = z;
-    xi += times_pinned<true>(relax, z);
-    x[i] = xi;
-}
-#undef DILU_STREAM_PROLOGUE
 
 // block forward: w_i = Einv_i (rhs_i - sum_{color(j)<c} A_ij w_j); w
 // pre-zeroed so the full-row product only picks up earlier colors.
@@ -1177,28 +1165,32 @@ __global__ __launch_bounds__(AMGX_BLOCK) void dilu_bwd_block_sorted(
 // single-workgroup launch runs `sweeps` whole applies back to back, every
 // forward and backward color of each, with __syncthreads as the color
 // barrier, where the per-color path pays 2 x colors + 1 launches per apply.
-// The arithmetic is that of the per-color kernels above, expression for
-// expression, so the two paths give the same bits: FUSED sweeps the full
-// slab (ro_f, ci_f, va_f) gathering the one vector y = x + w, which the
-// kernel itself rewrites as y = x + 0 at the start of every apply; plain
-// sweeps the L slab (same three arguments) gathering w. The backward sweep
-// runs over the U slab in place in w and carries x_i += relax z_i. Neither w
-// nor y is read before this launch has written it.
+// The rows run the rules of the per-color kernels above, so the two paths
+// give the same bits: FUSED sweeps the full slab (ro_f, ci_f, va_f) with
+// DiluFwdFull, the kernel itself rewriting y = x + 0 at the start of every
+// apply; plain sweeps the L slab (same three arguments) with DiluFwdLower;
+// the backward sweep runs DiluBwdUpper over the U slab. Neither w nor y is
+// read before this launch has written it.
 // LF / LU lanes per row of the forward / backward slab (slab_row_dot_lanes).
 // A color takes ceil(rows * LANES / blockDim) rounds; blockDim is a multiple
 // of LANES, so the lanes of a row share a round, and no thread leaves a
 // color before its barrier.
-template <int LANES, typename TA, typename TV, typename RowOp>
+template <int LANES, typename TA, typename TV, typename Rule>
 __device__ __forceinline__ void dilu_small_color(
     const int* __restrict__ ro, const int* __restrict__ ci,
-    const TA* __restrict__ va, const TV* v, int s0, int s1, RowOp row_op) {
+    const TA* __restrict__ va, const int* __restrict__ rows, int s0, int s1,
+    const Rule& rule) {
     const int lane = threadIdx.x & (LANES - 1);
     const int per_round = blockDim.x / LANES;
     for (int t0 = s0; t0 < s1; t0 += per_round) {
         int t = t0 + threadIdx.x / LANES;
         if (t < s1) {   // uniform over the lanes of a row
-            TV sum = slab_row_dot_lanes<LANES>(ro, ci, va, t, lane, v);
-            if (lane == 0) row_op(t, sum);
+            TV sum = slab_row_dot_lanes<LANES>(ro, ci, va, t, lane,
+                                               rule.gathered());
+            if (lane == 0) {
+                int i = rows[t];
+                rule.template finish<false>(i, rule.read(t, i), sum);
+            }
         }
     }
     __syncthreads();
@@ -1212,32 +1204,25 @@ __global__ __launch_bounds__(1024) void dilu_small_kernel(
     const TA* __restrict__ einv_s, const int* __restrict__ rows,
     const int* __restrict__ bounds, int ncolors, const TV* __restrict__ rhs,
     TV* w, TV* y, TV* x, TV relax, long long vec_n, int sweeps) {
+    const auto fwd = [&] {
+        if constexpr (FUSED)
+            return DiluFwdFull<TA, TV>{einv_s, rhs, x, w, y};
+        else
+            return DiluFwdLower<TA, TV>{einv_s, rhs, w};
+    }();
+    const DiluBwdUpper<TA, TV> bwd{einv_s, w, x, relax};
     for (int sw = 0; sw < sweeps; ++sw) {
         if constexpr (FUSED) {
             for (long long j = threadIdx.x; j < vec_n; j += blockDim.x)
                 y[j] = x[j] + TV(0);
             __syncthreads();
         }
-        for (int c = 0; c < ncolors; ++c) {
-            dilu_small_color<LF, TA, TV>(
-                ro_f, ci_f, va_f, FUSED ? y : w, bounds[c], bounds[c + 1],
-                [&](int t, TV sum) {
-                    int i = rows[t];
-                    TV wi = (TV)einv_s[t] * (rhs[i] - sum);
-                    w[i] = wi;
-                    if constexpr (FUSED) y[i] = add_unfused(x[i], wi);
-                });
-        }
-        for (int c = ncolors - 1; c >= 0; --c) {
-            dilu_small_color<LU, TA, TV>(
-                ro_u, ci_u, va_u, w, bounds[c], bounds[c + 1],
-                [&](int t, TV sum) {
-                    int i = rows[t];
-                    TV z = w[i] - (TV)einv_s[t] * sum;
-                    w[i] = z;
-                    x[i] += relax * z;
-                });
-        }
+        for (int c = 0; c < ncolors; ++c)
+            dilu_small_color<LF, TA, TV>(ro_f, ci_f, va_f, rows, bounds[c],
+                                         bounds[c + 1], fwd);
+        for (int c = ncolors - 1; c >= 0; --c)
+            dilu_small_color<LU, TA, TV>(ro_u, ci_u, va_u, rows, bounds[c],
+                                         bounds[c + 1], bwd);
     }
 }
 
@@ -1369,25 +1354,30 @@ void dilu_bwd_sorted(const int* ro_s, const int* ci_s, const TA* va_s,
     }
 }
 
-// LANES of a scalar per-color launch: 1 or 8 lanes per row, or DILU_STREAM
-// for the stream form `skernel`
-#define DILU_LANES_LAUNCH(kernel, skernel, lanes, count, s, ...)               \
-    do {                                                                       \
-        if ((lanes) == DILU_STREAM)                                            \
-            hipLaunchKernelGGL((skernel<TA, TV>),                              \
-                               dim3(dilu_stream_grid(count)),                  \
-                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
-        else if ((lanes) == 8)                                                 \
-            hipLaunchKernelGGL((kernel<8, TA, TV>),                            \
-                               dim3(grid_1d((long long)(count) * 8)),          \
-                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
-        else if ((lanes) == 1)                                                 \
-            hipLaunchKernelGGL((kernel<1, TA, TV>), dim3(grid_1d(count)),      \
-                               dim3(AMGX_BLOCK), 0, s, __VA_ARGS__);           \
-        else                                                                   \
-            throw std::runtime_error(                                          \
-                #kernel ": lanes must be 1, 8 or DILU_STREAM");                \
-    } while (0)
+// One color of a scalar per-color sweep: 1 or 8 lanes per row, or
+// DILU_STREAM for the stream shape
+template <typename TA, typename TV, typename Rule>
+void dilu_lanes_launch(const char* name, int lanes, const int* ro,
+                       const int* ci, const TA* va, const int* rows,
+                       int count, Rule rule, hipStream_t s) {
+    if (count <= 0) return;
+    if (lanes == DILU_STREAM)
+        hipLaunchKernelGGL((dilu_stream_kernel<TA, TV, Rule>),
+                           dim3(dilu_stream_grid(count)), dim3(AMGX_BLOCK), 0,
+                           s, ro, ci, va, rows, count, rule);
+    else if (lanes == 8)
+        hipLaunchKernelGGL((dilu_lane_kernel<8, TA, TV, Rule>),
+                           dim3(grid_1d((long long)count * 8)),
+                           dim3(AMGX_BLOCK), 0, s, ro, ci, va, rows, count,
+                           rule);
+    else if (lanes == 1)
+        hipLaunchKernelGGL((dilu_lane_kernel<1, TA, TV, Rule>),
+                           dim3(grid_1d(count)), dim3(AMGX_BLOCK), 0, s, ro,
+                           ci, va, rows, count, rule);
+    else
+        throw std::runtime_error(std::string(name) +
+                                 ": lanes must be 1, 8 or DILU_STREAM");
+}
 
 template <typename TV>
 void dilu_y_init(const TV* x, TV* y, long long n, hipStream_t s) {
@@ -1401,32 +1391,27 @@ void dilu_fwd_full(const int* ro_s, const int* ci_s, const TA* va_s,
                    const TA* einv_s, const int* rows, int count,
                    const TV* rhs, const TV* x, TV* w, TV* y, int lanes,
                    hipStream_t s) {
-    if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_fwd_scalar_full, dilu_fwd_stream_full, lanes,
-                      count, s, ro_s, ci_s, va_s, einv_s, rows, count, rhs, x,
-                      w, y);
+    dilu_lanes_launch<TA, TV>("dilu_fwd_full", lanes, ro_s, ci_s, va_s, rows,
+                              count,
+                              DiluFwdFull<TA, TV>{einv_s, rhs, x, w, y}, s);
 }
 
 template <typename TA, typename TV>
 void dilu_fwd_lower(const int* ro_l, const int* ci_l, const TA* va_l,
                     const TA* einv_s, const int* rows, int count,
                     const TV* rhs, TV* w, int lanes, hipStream_t s) {
-    if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_fwd_scalar_lower, dilu_fwd_stream_lower, lanes,
-                      count, s, ro_l, ci_l, va_l, einv_s, rows, count, rhs,
-                      w);
+    dilu_lanes_launch<TA, TV>("dilu_fwd_lower", lanes, ro_l, ci_l, va_l, rows,
+                              count, DiluFwdLower<TA, TV>{einv_s, rhs, w}, s);
 }
 
 template <typename TA, typename TV>
 void dilu_bwd_upper(const int* ro_u, const int* ci_u, const TA* va_u,
                     const TA* einv_s, const int* rows, int count, TV* w,
                     TV* x, TV relax, int lanes, hipStream_t s) {
-    if (count <= 0) return;
-    DILU_LANES_LAUNCH(dilu_bwd_scalar_upper, dilu_bwd_stream_upper, lanes,
-                      count, s, ro_u, ci_u, va_u, einv_s, rows, count, w, x,
-                      relax);
+    dilu_lanes_launch<TA, TV>("dilu_bwd_upper", lanes, ro_u, ci_u, va_u, rows,
+                              count,
+                              DiluBwdUpper<TA, TV>{einv_s, w, x, relax}, s);
 }
-#undef DILU_LANES_LAUNCH
 
 // ============================================================ transfers
 template <typename T>
